@@ -1,16 +1,27 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the HIP engine on BASELINE.json's configs, one JSON line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6] [--full]
+                  [--dump-outputs DIR]
 
 Default (`--config 2`, BASELINE configs[1], the configuration the metric is quoted on): an
 ensemble of 1024 independent advective-diffusive Columns per GPU, nz=100, fp64.  A bench
 "step" is one pass of the hot path over the rank's batch: ONE launch that advances every
 column by `--steps-per-launch` (default 1000 = the config's whole job; wA is static) model
 time steps.  `value` counts Column.timestep calls: columns x K x steps-per-launch / time.
-At N=1 the same line also carries, under "coupled", the driver-run numbers of the coupled
-configs 3, 4 and 5 at their SURVEY 8d sizes and full run lengths (2400 / 2400 / 3600 model
-steps), each with its dominant kernel's roofline and a CPU baseline.
+
+A plain run sets up, warms up, times the K steps and prints the line; its roofline block is
+computed from that timed run.  Everything that takes runs of its own is behind `--full`: the
+contracted (tolerance) mode, the one-step and HBM-regime entries of config 2, the run-average
+kernel breakdown and roofline of a coupled headline, the CPU baselines and, at N=1, the blocks
+"c6", "c3", "c4", "c5": the driver-run numbers of the coupled configs at their SURVEY 8d sizes
+and full run lengths (2400 / 2400 / 3600 model steps), each with its dominant kernel's roofline
+and a CPU baseline.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last
+step as DIR/<name>.npy (float64): config 2 the buoyancy `b` of every column (ColumnBatch.get_b),
+a coupled config the arrays of its ensemble's state().  Rank 0 writes its own members.  The
+inputs are seeded (pymoc_amd.configs), so the same arguments give the same inputs in every run.
 
 `--config 3|4|5` makes a coupled config the headline instead: a bench step is then one
 MOC-update interval (MOC_up_iters model steps of both columns [+ the mixed layer] and one
@@ -31,9 +42,9 @@ configs' blocks "c3", "c4", "c5", so that a record keeping only the tail of the 
 them.  Every coupled roofline is computed from the RUN-AVERAGE duration of the dominant kernel:
 HIP events around every launch of a full-length run (pymoc_amd.device.LaunchTimer).
 
-The CPU baselines (oracle/, the plain-C restatement of the reference's algorithm driven
-member by member like the reference's loops) are timed FIRST, before this process touches
-the GPU: on 1 core and on all cores this process may use (`multiprocessing`, fork).
+The CPU baselines (`--full`; oracle/, the plain-C restatement of the reference's algorithm
+driven member by member like the reference's loops) are timed FIRST, before this process
+touches the GPU: on 1 core and on all cores this process may use (`multiprocessing`, fork).
 """
 import argparse
 import json
@@ -193,6 +204,30 @@ def load_json(path):
     return {}
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+  """--dump-outputs: every array of `arrays` ({name: array whose rows are members}) as
+  <path>/<name>.npy in float64.  Above `limit` bytes in all, the same fixed, seeded sample of
+  member rows is kept of every array, and its (sorted) row indices go to member_index.npy."""
+  arrs = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+  total = sum(a.nbytes for a in arrs.values())
+  if total > limit:
+    n = {a.shape[0] for a in arrs.values()}
+    assert len(n) == 1, "outputs with different member counts: %s" % sorted(n)
+    n = n.pop()
+    per_row = total / float(n)
+    keep = max(1, int((limit - 8 * n) // (per_row + 8)))
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(keep, n), replace=False))
+    arrs = {k: a[idx] for k, a in arrs.items()}
+    arrs["member_index"] = idx.astype(np.float64)
+  os.makedirs(path, exist_ok=True)
+  for k, a in arrs.items():
+    np.save(os.path.join(path, k + ".npy"), a)
+  return sorted(arrs)
+
+
 def run_steps(batch, wA, dt, nsteps, per_launch, lanes, arith="exact"):
   """Exactly nsteps steps as ceil(nsteps/per_launch) launches; returns launch count."""
   done, launches = 0, 0
@@ -275,22 +310,26 @@ def bench_config2(args, env):
   kernel_ms = ev0.elapsed_ms(ev1)
   nonfinite = int(batch.get_nonfinite().sum())
   b_final = batch.get_b()
-  # the opt-in tolerance mode (PM_OP_CONTRACTED) on a copy of the same ensemble, same K launches
-  # (every rank runs it: no collective inside)
-  tol = pymoc_amd.ColumnBatch(cfg["z"], cfg["kappa"], cfg["Area"], cfg["b0"], bs=cfg["bs"],
-                              bbot=cfg["bbot"], N2min=cfg["N2min"], do_conv=cfg["do_conv"],
-                              stream=stream)
-  run_steps(tol, wA, dt, W * F, F, args.lanes, arith="contracted")
-  stream.sync()
-  ev2, ev3 = Event(), Event()
-  ev2.record(stream)
-  run_steps(tol, wA, dt, K * F, F, args.lanes, arith="contracted")
-  ev3.record(stream)
-  stream.sync()
-  tol_ms = ev2.elapsed_ms(ev3) / launches
-  tol_b = tol.get_b()
-  tol_err = float(np.max(np.abs(tol_b - b_final)) / np.max(np.abs(b_final)))
-  del tol
+  if rank == 0 and getattr(args, "dump_outputs", None):
+    dump_outputs(args.dump_outputs, {"b": b_final})
+  full = getattr(args, "full", False)
+  if full:
+    # the opt-in tolerance mode (PM_OP_CONTRACTED) on a copy of the same ensemble, same K
+    # launches (every rank runs it: no collective inside)
+    tol = pymoc_amd.ColumnBatch(cfg["z"], cfg["kappa"], cfg["Area"], cfg["b0"], bs=cfg["bs"],
+                                bbot=cfg["bbot"], N2min=cfg["N2min"], do_conv=cfg["do_conv"],
+                                stream=stream)
+    run_steps(tol, wA, dt, W * F, F, args.lanes, arith="contracted")
+    stream.sync()
+    ev2, ev3 = Event(), Event()
+    ev2.record(stream)
+    run_steps(tol, wA, dt, K * F, F, args.lanes, arith="contracted")
+    ev3.record(stream)
+    stream.sync()
+    tol_ms = ev2.elapsed_ms(ev3) / launches
+    tol_b = tol.get_b()
+    tol_err = float(np.max(np.abs(tol_b - b_final)) / np.max(np.abs(b_final)))
+    del tol
   if rank != 0:
     return None
 
@@ -322,11 +361,12 @@ def bench_config2(args, env):
                  "gather_overlap": not getattr(args, "gather_inline", False),
                  "collectives": getattr(diag, "ncollectives", 0)},
       "nonfinite": nonfinite, "checksum": float(np.sum(b_final)),
-      "contracted": {"value": sig(C * F / (tol_ms * 1e-3)), "kernel_us": sig(tol_ms * 1e3),
-                     "frac": sig(flop / (tol_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 4),
-                     "max_rel_diff": sig(tol_err, 3)},
   }
-  if not args.no_single_step:
+  if full:
+    out["contracted"] = {"value": sig(C * F / (tol_ms * 1e-3)), "kernel_us": sig(tol_ms * 1e3),
+                         "frac": sig(flop / (tol_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 4),
+                         "max_rel_diff": sig(tol_err, 3)}
+  if full and not args.no_single_step:
     # one step per launch (b, wA and the static coefficients cross HBM/L2 every step): the
     # regime of BASELINE config 1 and of user loops that refresh Psi every step
     ms1 = time_calls(lambda: batch.steps(wA, dt, 1, lanes_per_col=args.lanes), 2000, stream,
@@ -340,7 +380,7 @@ def bench_config2(args, env):
         batch.steps(wA, dt, 1, lanes_per_col=args.lanes)
     msg = time_calls(lambda: cap.graph.launch(stream), 40, stream, Event, warm=5)
     out["single_step_graph_us"] = sig(msg * 1e3 / 64)
-  if not args.no_single_step and world == 1 and C == 1024 and nz == 100:
+  if full and not args.no_single_step and world == 1 and C == 1024 and nz == 100:
     # the SAME kernel where HBM does bind: one step per launch on an ensemble far beyond the
     # caches (262144 columns: 0.84 ... 1.26 GB cross HBM per launch)
     Cb = 262144
@@ -537,9 +577,12 @@ def headline_coupled(config, args, env):
   res, ens = bench_coupled(config, args, env, members, sharded=True)
   M, nz = ens.M, int(ens.nz)
   diag_iters = ens.diag_iters
+  if env["rank"] == 0 and getattr(args, "dump_outputs", None):
+    dump_outputs(args.dump_outputs, ens.state())
   del ens
   roof = None
-  if env["rank"] == 0:  # (no collective inside: the other ranks go straight to the final barrier)
+  if env["rank"] == 0 and getattr(args, "full", False):
+    # (no collective inside: the other ranks go straight to the final barrier)
     _, roof = kernel_breakdown(config, env, members, args.steps * M, args.warmup)
   if env["rank"] != 0:
     return None
@@ -617,10 +660,17 @@ def main():
                   help="members (columns) per GPU; 0 = the SURVEY 8d size of the config")
   ap.add_argument("--nz", type=int, default=100, help="config 2 only")
   ap.add_argument("--lanes", type=int, default=0, help="config 2: lanes per column (0 = auto)")
-  ap.add_argument("--no-cpu-baseline", action="store_true")
-  ap.add_argument("--no-single-step", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="also measure what takes runs of its own: CPU baselines, the contracted "
+                       "mode, config 2's one-step and HBM-regime entries, kernel breakdowns and "
+                       "rooflines of coupled configs, and (config 2 at N=1) the c6/c3/c4/c5 blocks")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the timed path computed in its last step as DIR/<name>.npy")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+  ap.add_argument("--no-single-step", action="store_true",
+                  help="with --full, config 2: skip the one-step and HBM-regime entries")
   ap.add_argument("--no-coupled", action="store_true",
-                  help="config 2 at N=1: skip the configs 3-5 entries")
+                  help="with --full, config 2 at N=1: skip the configs 3-6 entries")
   ap.add_argument("--cpu-workers", type=int, default=0, help="cap of the all-core baseline")
   ap.add_argument("--cpu-seconds", type=float, default=6.0, help="budget per baseline leg")
   ap.add_argument("--gather", choices=("all", "root"), default="root",
@@ -638,6 +688,8 @@ def main():
   ap.add_argument("--force-rccl", action="store_true",
                   help="use the RCCL communicator even with one rank (plumbing check)")
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be >= 1 and --warmup >= 0")
 
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     # plain `python bench.py --gpus N`: start the N ranks ourselves, before anything here
@@ -658,8 +710,8 @@ def main():
 
   # CPU baselines first: nothing below this block has touched the GPU yet
   cpu = {}
-  want_coupled = args.config == 2 and world == 1 and not args.no_coupled
-  if world == 1 and rank == 0 and not args.no_cpu_baseline:
+  want_coupled = args.full and args.config == 2 and world == 1 and not args.no_coupled
+  if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
     for c in ([args.config] + ([3, 4, 5, 6] if want_coupled else [])):
       cpu[c] = cpu_baseline(c, args.nz if c == 2 else 100, args.cpu_seconds, args.cpu_seconds,
                             args.cpu_workers)

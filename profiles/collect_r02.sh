@@ -13,9 +13,9 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_r02
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-FULL="python3 $REPO/bench.py --no-cpu-baseline"
-K1="python3 $REPO/bench.py --no-cpu-baseline --no-single-step --no-coupled"
-CAL="python3 $REPO/bench.py --no-cpu-baseline --no-single-step --no-coupled --columns 262144 --steps 20 --warmup 2 --steps-per-launch 1"
+FULL="python3 $REPO/bench.py --full --no-cpu-baseline"
+K1="python3 $REPO/bench.py --full --no-cpu-baseline --no-single-step --no-coupled"
+CAL="python3 $REPO/bench.py --full --no-cpu-baseline --no-single-step --no-coupled --columns 262144 --steps 20 --warmup 2 --steps-per-launch 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $FULL > $OUT/bench_traced.json 2> $OUT/err.txt
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $OUT/pmc_sq -- $K1 > $OUT/bench_sq.json 2>> $OUT/err.txt
 rocprofv3 --pmc SQ_INSTS_BRANCH SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_ANY SQ_IFETCH --output-format csv -d $OUT/pmc_sq2 -- $K1 > /dev/null 2>> $OUT/err.txt

@@ -4,8 +4,8 @@
 #   gpurun_out/r03/c<N>/trace   rocprofv3 --kernel-trace --stats        (average kernel durations)
 #   gpurun_out/r03/c<N>/pmc<k>  rocprofv3 --pmc ... in passes of their own (never with tracing)
 #   gpurun_out/r03/c<N>/bench.json  the bench line of the traced run
-# c2 = bench.py --config 2 (headline kernel + contracted mode; --no-coupled), c2s = the same
-# with the one-step / HBM-regime entries (k_column_stream), c3..c5 = bench.py --config 3|4|5.
+# c2 = bench.py --full --config 2 (headline kernel + contracted mode; --no-coupled), c2s = the same
+# with the one-step / HBM-regime entries (k_column_stream), c3..c5 = bench.py --full --config 3|4|5.
 # Summarised by profiles/summarize_r03.py into profiles/r03/ (tracked) -- copy, do not cite
 # gpurun_out/.  NOTE gpurun MERGES the box's gpurun_out/ into the local one: delete the local
 # gpurun_out/r03 of an earlier collection before summarising.
@@ -16,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {  # name, bench args
   local name=$1; shift
   local D=$OUT/$name; mkdir -p $D
-  local CMD="python3 $REPO/bench.py --no-cpu-baseline $*"
+  local CMD="python3 $REPO/bench.py --full --no-cpu-baseline $*"
   local T="timeout -k 10 300"   # (a pass that dies must not hold the box)
   $T rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- $CMD > $D/bench.json 2>> $D/err.txt
   echo "$name trace done"

@@ -4,8 +4,8 @@
 #   gpurun_out/r05/c<N>/trace   rocprofv3 --kernel-trace --stats        (average kernel durations)
 #   gpurun_out/r05/c<N>/pmc<k>  rocprofv3 --pmc ... in passes of their own (never with tracing)
 #   gpurun_out/r05/c<N>/bench.json  the bench line of the traced run
-# c2 = bench.py --config 2 (headline kernel + contracted mode; --no-coupled), c2s = the same
-# with the one-step / HBM-regime entries (k_column_stream); c3, c4, c5, c6 = bench.py --config N
+# c2 = bench.py --full --config 2 (headline kernel + contracted mode; --no-coupled), c2s = the same
+# with the one-step / HBM-regime entries (k_column_stream); c3, c4, c5, c6 = bench.py --full --config N
 # --breakdown-only: the FULL-LENGTH run (10 warm-up intervals + 2400 / 2400 / 3600 / 2400 steps)
 # whose HIP-event averages the default line's c<N> blocks report, so that every `frac` of the
 # line recomputes from <c>_kernel_stats.csv (config 4 / 6: the update's launches one after the
@@ -20,7 +20,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {  # name, bench args
   local name=$1; shift
   local D=$OUT/$name; mkdir -p $D
-  local CMD="python3 $REPO/bench.py --no-cpu-baseline $*"
+  local CMD="python3 $REPO/bench.py --full --no-cpu-baseline $*"
   local T="timeout -k 10 300"   # (a pass that dies must not hold the box)
   $T rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- $CMD > $D/bench.json 2>> $D/err.txt
   echo "$name trace done"

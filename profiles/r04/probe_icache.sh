@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/r04_icache
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $REPO/bench.py --no-cpu-baseline --config 4 --steps 10 --warmup 2"
+CMD="python3 $REPO/bench.py --full --no-cpu-baseline --config 4 --steps 10 --warmup 2"
 timeout -k 10 300 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_WAVES --output-format csv -d $OUT/pmc1 -- $CMD > /dev/null 2>> $OUT/err.txt
 timeout -k 10 300 rocprofv3 --pmc SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_WAVES --output-format csv -d $OUT/pmc2 -- $CMD > /dev/null 2>> $OUT/err.txt
 find $OUT -name "*agent_info*" -delete

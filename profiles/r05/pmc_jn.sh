@@ -7,7 +7,7 @@ rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for v in split nosplit; do
   if [ $v = split ]; then export PYMOC_JN_SPLIT=1; else unset PYMOC_JN_SPLIT; fi
-  timeout -k 10 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_LDS --output-format csv -d $OUT/$v -- python3 $REPO/bench.py --no-cpu-baseline --config 5 --steps 10 --warmup 2 > $OUT/$v.json 2>> $OUT/err.txt || { echo "$v failed"; tail -5 $OUT/err.txt; exit 1; }
+  timeout -k 10 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_LDS --output-format csv -d $OUT/$v -- python3 $REPO/bench.py --full --no-cpu-baseline --config 5 --steps 10 --warmup 2 > $OUT/$v.json 2>> $OUT/err.txt || { echo "$v failed"; tail -5 $OUT/err.txt; exit 1; }
   echo "$v done"
   find $OUT/$v -name "*agent_info*" -delete
 done

@@ -10,7 +10,7 @@ out=gpurun_out/r05_gather.log
 for cfg in 4 5; do
   for extra in "" "--force-rccl" "--force-rccl --gather-inline" "--force-rccl --gather all" "--force-rccl --gather all --gather-inline"; do
     echo "== config $cfg $extra" >> $out
-    timeout -k 10 300 python bench.py --config $cfg --steps 100 --warmup 10 --no-cpu-baseline $extra 2>&1 \
+    timeout -k 10 300 python bench.py --full --config $cfg --steps 100 --warmup 10 --no-cpu-baseline $extra 2>&1 \
       | python -c "
 import sys, json
 for ln in sys.stdin:

@@ -184,10 +184,12 @@ def test_explicit_stream_equals_default_stream(gpu):
 
 
 @pytest.mark.parametrize("args,nfields", [
-    (["--config", "4", "--members", "512", "--steps", "20", "--warmup", "2"], 4),
-    (["--config", "4", "--members", "512", "--steps", "20", "--warmup", "2", "--gather", "all"], 4),
-    (["--config", "5", "--members", "256", "--steps", "20", "--warmup", "2"], 4),
-    (["--config", "5", "--members", "256", "--steps", "20", "--warmup", "2", "--gather-inline"], 4),
+    (["--config", "4", "--members", "512", "--steps", "20", "--warmup", "2", "--full"], 4),
+    (["--config", "4", "--members", "512", "--steps", "20", "--warmup", "2", "--gather", "all",
+      "--full"], 4),
+    (["--config", "5", "--members", "256", "--steps", "20", "--warmup", "2", "--full"], 4),
+    (["--config", "5", "--members", "256", "--steps", "20", "--warmup", "2", "--gather-inline",
+      "--full"], 4),
     (["--config", "2", "--steps", "3", "--warmup", "1", "--no-single-step"], 0),
 ])
 def test_bench_under_torch_distributed_run_with_rccl_one_rank(gpu, args, nfields):
