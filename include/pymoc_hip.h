@@ -678,6 +678,56 @@ int pm_selftest_so_scans(int32_t nhas, uint64_t seed, double *max_rel3, int32_t 
 /* debug/test: lane-shift primitive self check (DPP wave shifts vs ds_bpermute) */
 int pm_selftest_lane_shift(int32_t *mismatches);
 
+/* ------------------------------------------------------------------ sections
+ * pymoc.plotting's section interpolators, every member of an ensemble at once:
+ *   PM_SEC_CHANNEL  Interpolate_channel.__call__ (src/pymoc/plotting/interp_channel.py:40-62):
+ *                   bs on y, bn on z, isopycnals of constant slope from the channel surface;
+ *   PM_SEC_TWOCOL   Interpolate_twocol.__call__ (src/pymoc/plotting/interp_twocol.py:37-73):
+ *                   bs and bn on z, isopycnals between the two columns;
+ * evaluated on the query grid yq x zq as gridit does (src/pymoc/utils/gridit.py:24-30:
+ * out[m][i][j] = f(yq[i], zq[j])).  Profiles are np.interp'ed (make_func, utils/make_func.py:31-44)
+ * unless PM_SEC_BS_SCALAR / PM_SEC_BN_SCALAR make them a float (value + 0*x).  The root finds are
+ * scipy.optimize.brenth with SciPy 1.15.3's defaults (xtol 2e-12, rtol 4 eps, maxiter 100,
+ * scipy/optimize/Zeros/brenth.c) in the same IEEE fp64 operations, so a finite section is
+ * bit-identical to the reference's.  Where brenth raises, the point is NaN and its status says
+ * why: PM_SEC_ESIGN "f(a) and f(b) must have different signs" (ValueError), PM_SEC_ECONV
+ * "Failed to converge after 100 iterations." (RuntimeError), PM_SEC_ENAN the function value is
+ * NaN (SciPy's ValueError guard, optimize/_zeros_py.py:_wrap_nan_raise).
+ * Member m's bs row is bs[bs_offset + m * bs_stride ...] (in doubles), so rows of an ensemble's
+ * state (ColumnBatch.b, SOMLBatch.bs) are read in place; stride 0 shares one row.
+ * Fix-ups (applied to the member's LDS copy, never to the input):
+ *   PM_SEC_FIX_PLOT_OVERTURNING  channel: Plot_overturning.py:42-50 (bs[0] = bs[1] if bs[0] > bs[1],
+ *                                then bn[0] = bs[0] if bs[0] < bn[0]); twocol: :63-64 (bn[0] = bs[0])
+ *   PM_SEC_FIX_TWOBASIN          channel only: twobasin_NadeauJansen.py:176 (bs[-1] = bn[-1])
+ * Sizes: 2 <= ny, nz <= 1024 (the member's profiles and axes are staged in LDS), 1 <= nyq, nzq
+ * <= 1024.  y, z sorted ascending (as np.interp requires).                                  */
+#define PM_SEC_CHANNEL 0
+#define PM_SEC_TWOCOL 1
+#define PM_SEC_BS_SCALAR 1            /* flags: bs is a float per member (bs_len ignored)   */
+#define PM_SEC_BN_SCALAR 2            /* flags: bn is a float per member                    */
+#define PM_SEC_FIX_PLOT_OVERTURNING 1 /* fixups */
+#define PM_SEC_FIX_TWOBASIN 2
+#define PM_SEC_OK 0
+#define PM_SEC_ESIGN 1
+#define PM_SEC_ECONV 2
+#define PM_SEC_ENAN 3
+#define PM_SEC_MAX_LEVELS 1024
+typedef struct pm_sections {
+  int32_t n, kind, ny, nz;      /* members, PM_SEC_*, profile axes y[ny], z[nz]              */
+  int32_t nyq, nzq, flags, fixups;
+  const double *y, *z;          /* [ny], [nz] the classes' grids (l = y[ny-1], z[0] = bottom) */
+  const double *yq, *zq;        /* [nyq], [nzq] query grid                                   */
+  const double *bs;             /* channel: [ny] per member, twocol: [nz] per member          */
+  int64_t bs_offset, bs_stride; /* in doubles */
+  const double *bn;             /* [nz] per member                                           */
+  int64_t bn_offset, bn_stride;
+  double *out;                  /* [n][nyq][nzq] out: the section, NaN where brenth raised   */
+  uint8_t *status;              /* [n][nyq][nzq] out: PM_SEC_OK / ESIGN / ECONV / ENAN (or NULL) */
+  int32_t *first;               /* [n] out: first failing point i*nzq + j in gridit order, -1 none (or NULL) */
+} pm_sections;
+
+int pm_sections_grid(const pm_sections *sec, pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

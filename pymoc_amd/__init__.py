@@ -13,6 +13,7 @@ from .psi_so import PsiSOBatch
 from .so_ml import SOMLBatch
 from .equilibrium import ColumnEquiBatch
 from .equi_column import EquiColumnBatch
+from .sections import SectionBatch
 from . import modules
 from . import utils
 from .modules import Column, Psi_Thermwind, Psi_SO, SO_ML, Equi_Column
@@ -21,3 +22,4 @@ from . import sharding
 from .ensembles import (EquiIterationEnsemble, ColumnThermwindEnsemble, TwoColEnsemble, JN2018Ensemble,
                         TwoBasinEnsemble)
 from . import diagnostics
+from . import plotting

@@ -136,6 +136,25 @@ class pm_jn2018(C.Structure):
   ]
 
 
+PM_SEC_CHANNEL, PM_SEC_TWOCOL = 0, 1
+PM_SEC_BS_SCALAR, PM_SEC_BN_SCALAR = 1, 2
+PM_SEC_FIX_PLOT_OVERTURNING, PM_SEC_FIX_TWOBASIN = 1, 2
+PM_SEC_OK, PM_SEC_ESIGN, PM_SEC_ECONV, PM_SEC_ENAN = 0, 1, 2, 3
+PM_SEC_MAX_LEVELS = 1024
+
+
+class pm_sections(C.Structure):
+  """Mirror of `struct pm_sections` (include/pymoc_hip.h)."""
+  _fields_ = [
+      ("n", C.c_int32), ("kind", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+      ("nyq", C.c_int32), ("nzq", C.c_int32), ("flags", C.c_int32), ("fixups", C.c_int32),
+      ("y", c_dp), ("z", c_dp), ("yq", c_dp), ("zq", c_dp),
+      ("bs", c_dp), ("bs_offset", C.c_int64), ("bs_stride", C.c_int64),
+      ("bn", c_dp), ("bn_offset", C.c_int64), ("bn_stride", C.c_int64),
+      ("out", c_dp), ("status", c_dp), ("first", c_dp)
+  ]
+
+
 PM_PACK_MAX_ITEMS = 8
 
 
@@ -247,6 +266,7 @@ SIGNATURES = {
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "pm_selftest_so_scans": (C.c_int, [C.c_int32, C.c_uint64, C.POINTER(C.c_double),
                                        C.POINTER(C.c_int32)]),
+    "pm_sections_grid": (C.c_int, [C.POINTER(pm_sections), C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
