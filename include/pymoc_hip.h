@@ -728,6 +728,48 @@ typedef struct pm_sections {
 
 int pm_sections_grid(const pm_sections *sec, pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Convergence check of an ensemble run to steady state (pymoc_amd.run_to_steady), ONE launch
+ * over the n rows of the current batch.  Row m holds original member k = orig[m]; rows whose
+ * member is no longer PM_STEADY_RUNNING are not touched.  For a running member:
+ *   d = max over the drift fields f and levels i of |src_f[m][i] - buf_f[m][i]|  (fmax: exact,
+ *       independent of order -- bitwise np.max(np.abs(cur - ref)) * scale);
+ *   drift_out[k] = d * scale (NaN when an element of src or snapshot is non-finite), then the
+ *       snapshot row buf_f[m] = src_f[m];
+ *   non-finite element -> PM_STEADY_NONFINITE; else streak[k] = (d * scale <= tol[k]) ?
+ *       streak[k] + 1 : 0, PM_STEADY_CONVERGED when streak[k] >= consecutive; else with
+ *       `finalize` PM_STEADY_MAXSTEPS;
+ *   a member that retires here has every capture field's src row copied to buf_c[k] and
+ *       step_out[k] = step;
+ *   members still running are counted into *n_running (zeroed by this entry first).
+ * Sizes: 0 <= n <= n0, 1 <= ndrift <= 4, 0 <= ncapture <= 8, consecutive >= 1, every field
+ * len >= 1 and src_stride >= len (doubles).                                                   */
+#define PM_STEADY_RUNNING 0
+#define PM_STEADY_CONVERGED 1
+#define PM_STEADY_NONFINITE 2
+#define PM_STEADY_MAXSTEPS 3
+#define PM_STEADY_MAX_DRIFT 4
+#define PM_STEADY_MAX_CAPTURE 8
+typedef struct pm_steady_field {
+  const double *src; int64_t src_stride; /* row m of the live state at src + m*src_stride        */
+  double *buf;                           /* drift field: snapshot [n][len]; capture: result [n0][len] */
+  int32_t len, reserved;
+} pm_steady_field;
+struct pm_steady_check {
+  int32_t n, n0, ndrift, ncapture;       /* rows now, members at the start, <=4 drift, <=8 capture */
+  int32_t consecutive, finalize;
+  int64_t step;                          /* steps taken at this check                             */
+  double scale;                          /* drift = scale * max |src - snapshot|                   */
+  const int32_t *orig;                   /* [n]  original member of row m                          */
+  const double *tol;                     /* [n0] per member                                        */
+  int32_t *streak, *status;              /* [n0] in/out                                            */
+  double *drift_out; int64_t *step_out;  /* [n0]                                                   */
+  int32_t *n_running;                    /* [1]  out, zeroed by the entry before the launch        */
+  pm_steady_field drift[PM_STEADY_MAX_DRIFT], capture[PM_STEADY_MAX_CAPTURE];
+};
+/* the struct is named by its tag only: a typedef of the same name would clash with the function */
+int pm_steady_check(const struct pm_steady_check *c, pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,3 +23,5 @@ from .ensembles import (EquiIterationEnsemble, ColumnThermwindEnsemble, TwoColEn
                         TwoBasinEnsemble)
 from . import diagnostics
 from . import plotting
+from . import steady
+from .steady import run_to_steady, SteadyResult

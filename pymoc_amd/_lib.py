@@ -181,6 +181,28 @@ class pm_jn2018_loop(C.Structure):
               ("sched", pm_run_schedule)]
 
 
+PM_STEADY_RUNNING, PM_STEADY_CONVERGED, PM_STEADY_NONFINITE, PM_STEADY_MAXSTEPS = 0, 1, 2, 3
+PM_STEADY_MAX_DRIFT, PM_STEADY_MAX_CAPTURE = 4, 8
+
+
+class pm_steady_field(C.Structure):
+  """Mirror of `struct pm_steady_field` (include/pymoc_hip.h)."""
+  _fields_ = [("src", c_dp), ("src_stride", C.c_int64), ("buf", c_dp), ("len", C.c_int32),
+              ("reserved", C.c_int32)]
+
+
+class pm_steady_check(C.Structure):
+  """Mirror of `struct pm_steady_check` (include/pymoc_hip.h)."""
+  _fields_ = [
+      ("n", C.c_int32), ("n0", C.c_int32), ("ndrift", C.c_int32), ("ncapture", C.c_int32),
+      ("consecutive", C.c_int32), ("finalize", C.c_int32), ("step", C.c_int64),
+      ("scale", C.c_double), ("orig", c_dp), ("tol", c_dp), ("streak", c_dp), ("status", c_dp),
+      ("drift_out", c_dp), ("step_out", c_dp), ("n_running", c_dp),
+      ("drift", pm_steady_field * PM_STEADY_MAX_DRIFT),
+      ("capture", pm_steady_field * PM_STEADY_MAX_CAPTURE)
+  ]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -267,6 +289,7 @@ SIGNATURES = {
     "pm_selftest_so_scans": (C.c_int, [C.c_int32, C.c_uint64, C.POINTER(C.c_double),
                                        C.POINTER(C.c_int32)]),
     "pm_sections_grid": (C.c_int, [C.POINTER(pm_sections), C.c_void_p]),
+    "pm_steady_check": (C.c_int, [C.POINTER(pm_steady_check), C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

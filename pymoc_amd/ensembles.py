@@ -626,6 +626,17 @@ class JN2018Ensemble(object):
       self.ii += 1
       remaining -= 1
 
+  def moc_update(self):
+    """The MOC update of the current step (run_JansenNadeau_2018.py:204-217) ahead of run(), so
+    that Psi / Psi_SO of this step can be read before it is taken; run() does not repeat it.
+    Only at a step the script updates at (ii % MOC_up_iters == 0)."""
+    if self.ii % self.M:
+      raise ValueError("step %d is not a MOC update step (MOC_up_iters=%d)" % (self.ii, self.M))
+    if self._updated_at != self.ii:
+      self._update()
+      self._after_update()
+      self._updated_at = self.ii
+
   def state(self):
     b = self.cols.get_b()
     return dict(b_basin=b[:self.n], b_north=b[self.n:], bs_SO=self.ml.bs.download(stream=self.stream),
