@@ -52,6 +52,7 @@ def _in_fast_range(x):
 
 
 _HINT_DIV3_OFF = 1 << 20  # (use_hints(div3=False): a bit outside the per-column flag bits)
+_ALIGNED_ADDRESS = 1 << 12  # stand-in for a DeviceArray's address in kernel_name (never dereferenced)
 
 
 def div3_proven(denominators):
@@ -281,22 +282,23 @@ class ColumnBatch(object):
     return g.value, p.value
 
   def kernel_name(self, nsteps, lanes_per_col=0, ops=_lib.PM_OP_TIMESTEP, horadv=False,
-                  arith="exact"):
-    """The kernel instantiation `steps(...)` of this shape launches (reporting only)."""
+                  arith="exact", precombined=False, wA=None):
+    """The kernel instantiation `steps(...)` with these arguments launches, as profilers name it
+    (`pm_column_kernel_name`; reporting only, "" when the call launches nothing).  `ops` may carry
+    PM_OP_WA_PSI / PM_OP_WA_TWOBASIN for `psi_forcing` / `twobasin_forcing`.  The 16-byte
+    alignment of the forcing steers the choice: `wA` is the DeviceArray `steps` gets; without it
+    the forcing is taken as aligned, as every DeviceArray is (host data goes through one)."""
+    if precombined:
+      ops = ops | _lib.PM_OP_WEFF
     if arith == "contracted":
       ops = ops | _lib.PM_OP_CONTRACTED
+    forcing = wA.ptr if isinstance(wA, DeviceArray) else _ALIGNED_ADDRESS
+    vdx = _ALIGNED_ADDRESS if horadv or ops & _lib.PM_OP_WA_TWOBASIN else None
+    d = self.descriptor()
     buf = C.create_string_buffer(96)
-    check(lib.pm_column_kernel_name(self.ncols, self.nz, int(lanes_per_col), int(nsteps),
-                                    int(ops), int(bool(horadv)), buf, 96))
-    name = buf.value.decode()
-    # the batch-wide PM_COLS_ALL_UNIFORM_AREA hint selects the scalar-Area instantiation
-    off = self.__dict__.get("_hints_off", 0)
-    if (self.uniform_area and not (off & _lib.PM_COL_UNIFORM_AREA) and
-        name.startswith("k_column_steps<64,") and name.endswith(",2,true>")):
-      # ... and PM_COLS_DIV3_PROVEN the 3-instruction quotients (division form 6)
-      div3 = self.div3_proven and not (off & _HINT_DIV3_OFF)
-      name = (name[:-len(",2,true>")] + ",6,true,true>") if div3 else (name[:-1] + ",true>")
-    return name
+    check(lib.pm_column_kernel_name(C.byref(d), forcing, vdx, int(nsteps), int(ops),
+                                    int(lanes_per_col), buf, 96))
+    return buf.value.decode()
 
   def combine_forcing(self, wA, out=None):
     """weff = wA - d(A kappa)/dz of each column's coefficient set in use, on the device

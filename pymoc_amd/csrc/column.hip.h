@@ -1023,8 +1023,6 @@ struct ColStageLean {
   double b[P], wA[P];
 };
 
-constexpr int STREAM_MAX_CPW = 64;  // columns per wave <= lanes (the scalars' vector load)
-
 // the wave's per-column scalars, lane i = column col0 + i
 struct StreamScalars {
   int flags, sel;
@@ -1263,12 +1261,8 @@ void k_column_stream(pm_columns c,
 }
 
 // columns per wave of the streaming kernel: enough waves to fill the chip several times over
+// (at most 64, the lanes of StreamScalars' vector load)
 inline int stream_cols_per_wave(int ncols) {
-  static const int forced = []() {
-    const char *e = getenv("PYMOC_STREAM_CPW");  // experiments (profiles/): 0 = automatic
-    return e ? atoi(e) : 0;
-  }();
-  if (forced > 0) return forced > STREAM_MAX_CPW ? STREAM_MAX_CPW : forced;
   // few, long waves: two rounds of four resident waves per SIMD; a wave's ramp of D columns is
   // paid once per cpw columns (measured at 262144 columns: 8 / 16 / 32 per wave -> 187 / 189 /
   // 181 us with the forcing precombined)
@@ -1294,197 +1288,191 @@ inline int pick_levels_per_lane(int G, int need) {
   return -1;
 }
 
-template <int G, int P>
-int launch_column_steps(const pm_columns &c, const double *wA, const double *vdx,
-                        const double *bin, double dt, int nsteps, int ops,
-                        hipStream_t st) {
-  const int cols_per_block = 256 / G;
-  const unsigned grid = (unsigned)((c.ncols + cols_per_block - 1) / cols_per_block);
-  const bool weff_in = (ops & PM_OP_WEFF) != 0;  // wA holds wA - d(A kappa)/dz
-  const bool contracted = (ops & PM_OP_CONTRACTED) != 0;  // tolerance mode (one wave per column)
-  // the kernel forms wA from Psi_iso / Psi_SO, or from the two-basin driver's overturnings (>= 3 steps)
-  const int wa_psi = ops & (PM_OP_WA_PSI | PM_OP_WA_TWOBASIN);
-  const double *const forcing2 = (ops & PM_OP_WA_TWOBASIN) ? vdx : nullptr;  // (horadv's slot)
-  if (forcing2) vdx = nullptr;  // no horadv with that modifier: the launch conditions below
-  ops &= ~(PM_OP_WEFF | PM_OP_CONTRACTED | PM_OP_WA_PSI | PM_OP_WA_TWOBASIN);
-  const double *const vk = forcing2 ? forcing2 : vdx;  // what the PLAIN kernels get in that slot
-  if constexpr (G == 64 && P <= 4) {
-    const int cpw = stream_cols_per_wave(c.ncols);
-    if (nsteps < 3 && ops == PM_OP_TIMESTEP && !vdx && cpw >= 2) {
-      const unsigned waves = (unsigned)((c.ncols + cpw - 1) / cpw);
-      // dt inside the exact-division window (in_fast_div_range, host side)
-      const double adt = dt < 0 ? -dt : dt;
-      const bool dt_ok = dt == 0.0 || (adt >= 0x1p-200 && adt <= 0x1p200);
+// Template arguments of a column kernel: k_column_steps<G, P, fast, plain, ua> or
+// k_column_stream<P, d, aff, lean, vec, d3, cpwu, wefft, uabt>
+struct ColKernel {
+  bool stream, plain, ua, aff, lean, vec, d3;
+  int fast, d, cpwu, wefft, uabt;
+  // the three general k_column_steps forms exist for every (G, P), the others for one wave per
+  // column and P <= 4, the 16-byte and straight-line forms for P = 2 only
+  constexpr bool compiled(int G, int P) const {
+    if (!stream && !ua && fast <= 2) return true;
+    return G == 64 && P <= 4 && (P == 2 || (!vec && cpwu == 0));
+  }
+};
+constexpr ColKernel col_steps(int fast, bool plain, bool ua = false) {
+  return {false, plain, ua, false, false, false, false, fast, 0, 0, -1, -1};
+}
+constexpr ColKernel col_stream(int d, bool aff = false, bool lean = false, bool vec = false,
+                               bool d3 = false, int cpwu = 0, int wefft = -1, int uabt = -1) {
+  return {true, false, false, aff, lean, vec, d3, 0, d, cpwu, wefft, uabt};
+}
+
+// The instantiations pm_column_steps launches: column_plan picks one row per call, and
+// launch_column_steps and column_kernel_name take its template arguments from that row.
+#define PM_COLUMN_KERNELS(X)                                                                   \
+  X(CK_STEPS_IEEE, col_steps(0, false))             /* 1-2 steps */                            \
+  X(CK_STEPS_RECIP, col_steps(1, false))            /* >= 3 steps: reciprocals formed once */  \
+  X(CK_STEPS_PLAIN, col_steps(2, true))             /* >= 3 plain timesteps */                 \
+  X(CK_STEPS_PLAIN_UA, col_steps(2, true, true))    /* ... every Area one number */            \
+  X(CK_STEPS_DIV3_UA, col_steps(6, true, true))     /* ... and 3-instruction quotients */      \
+  X(CK_STEPS_CONTRACTED, col_steps(4, true))        /* ... PM_OP_CONTRACTED */                 \
+  X(CK_STREAM, col_stream(2))                       /* 1-2 plain steps, large batch */         \
+  X(CK_STREAM_WEFF, col_stream(3))                  /* forcing precombined */                  \
+  X(CK_STREAM_AFF, col_stream(3, true))             /* kappa formed from its two factors */    \
+  X(CK_STREAM_WEFF_AFF, col_stream(4, true))                                                   \
+  X(CK_STREAM_LEAN, col_stream(5, true, true))      /* both, and every Area one number */      \
+  X(CK_STREAM_LEAN_VEC, col_stream(5, true, true, true))  /* ... 16-byte accesses */           \
+  X(CK_STREAM_LEAN_VEC_D3, col_stream(5, true, true, true, true))                              \
+  X(CK_STREAM_LEAN_VEC_U8, col_stream(5, true, true, true, false, 8))  /* straight-line */     \
+  X(CK_STREAM_LEAN_VEC_D3_U8, col_stream(5, true, true, true, true, 8))                        \
+  X(CK_STREAM_U8, col_stream(2, false, false, false, false, 8, 0, 0))                          \
+  X(CK_STREAM_WEFF_UA_U8, col_stream(3, false, false, false, false, 8, 1, 1))
+
+#define PM_CK_ID(id, args) id,
+enum ColKernelId { CK_NONE, PM_COLUMN_KERNELS(PM_CK_ID) };  // CK_NONE: the call launches nothing
+#undef PM_CK_ID
+constexpr ColKernel col_kernel(ColKernelId k) {
+#define PM_CK_ARGS(id, args) \
+  case id: return args;
+  switch (k) {
+    PM_COLUMN_KERNELS(PM_CK_ARGS)
+    default: return {};
+  }
+#undef PM_CK_ARGS
+}
+
+struct ColumnPlan {
+  ColKernelId kernel;
+  int G, P;       // lanes per column, levels per lane
+  int cpw;        // columns per wave (k_column_stream)
+  unsigned grid;  // blocks of 256 threads
+};
+
+// The launch of a pm_column_steps call that passed its checks and has steps to take; a function
+// of the call alone.  G, P: the batch's work decomposition.
+inline ColumnPlan column_plan(const pm_columns &c, const double *wA, const double *vdx, int nsteps,
+                              int ops, int G, int P) {
+  const bool weff = (ops & PM_OP_WEFF) != 0;  // wA holds wA - d(A kappa)/dz
+  // convect + vertadvdiff, no horadv (PM_OP_WA_TWOBASIN takes horadv's slot for its forcing)
+  const bool plain =
+      (ops & ~(PM_OP_WEFF | PM_OP_CONTRACTED | PM_OP_WA_PSI | PM_OP_WA_TWOBASIN)) == PM_OP_TIMESTEP &&
+      (!vdx || (ops & PM_OP_WA_TWOBASIN));
+  // PM_COLS_ALL_UNIFORM_AREA: the caller vouches that EVERY column carries PM_COL_UNIFORM_AREA
+  // (a kernel cannot branch per column on what its load ring holds)
+  const bool ua = (c.reserved & PM_COLS_ALL_UNIFORM_AREA) != 0;
+  const bool d3 = (c.reserved & PM_COLS_DIV3_PROVEN) != 0;  // (the caller's pm_div3_proven verdict)
+  const bool aff = c.kappa_base && c.kappa_profile && c.nsel == 1;
+  const bool wave_per_col = G == 64 && P <= 4;
+  const int cpw = stream_cols_per_wave(c.ncols);
+  ColumnPlan pl{CK_STEPS_IEEE, G, P, 0, (unsigned)((c.ncols + 256 / G - 1) / (256 / G))};
+  if (wave_per_col && nsteps < 3 && plain && cpw >= 2) {
+    pl.cpw = cpw;
+    if (weff && aff && ua) {
+      // the lean ring: b and weff of a column in flight.  Measured at 262144 columns x nz = 100
+      // (profiles/r04/probe_stream_lean.py): ring depth 4 / 5 / 6 / 8 -> 150.5 / 148.8 / 158.6 /
+      // 154.8 us at their best columns-per-wave; 16 columns per wave beat 32 (the non-lean forms'
+      // choice) and 8
+      pl.cpw = c.ncols / 16384 < 2 ? 2 : (c.ncols / 16384 > 16 ? 16 : c.ncols / 16384);
+      const bool vec = P == 2 && (c.nz & 1) == 0 &&
+                       ((((unsigned long long)c.b) | ((unsigned long long)wA)) & 15ull) == 0ull;
+      // every wave exactly 8 columns: the straight-line instantiation (CPWU).  Measured at 262144
+      // columns (profiles/r05/stream_variants.log): ring depth 3 / 4 / 5 / 6 at 16 columns per wave
+      // 132 / 133 / 133 / 134 us -- with a ring that works its depth no longer matters -- and depth
+      // 5 at 8 / 16 / 32 columns per wave 127 / 133 / 268 us
+      const bool u8 = vec && c.ncols % 8 == 0 && c.ncols >= 8 * 4096;
+      if (u8) pl.cpw = 8;
+      pl.kernel = !vec ? CK_STREAM_LEAN
+                  : u8 ? (d3 ? CK_STREAM_LEAN_VEC_D3_U8 : CK_STREAM_LEAN_VEC_U8)
+                       : (d3 ? CK_STREAM_LEAN_VEC_D3 : CK_STREAM_LEAN_VEC);
+    } else if (P == 2 && !aff && c.ncols % 8 == 0 && c.ncols >= 8 * 4096 && weff == ua) {
+      // the straight-line forms of the two other regimes the bench reports: forcing precombined
+      // and every Area one number (32 nz B per column-step), and the C-ABI default (48 nz B)
+      pl.cpw = 8;
+      pl.kernel = weff ? CK_STREAM_WEFF_UA_U8 : CK_STREAM_U8;
+    } else {
       // stages of the load ring: three arrays per column with the forcing precombined, five
       // without (the ring's registers bound the occupancy)
-      const bool aff = c.kappa_base && c.kappa_profile && c.nsel == 1;
-      // PM_COL_BATCH_UNIFORM_AREA in reserved: the caller vouches that EVERY column carries
-      // PM_COL_UNIFORM_AREA (the kernel cannot branch per column on what its ring holds)
-      const bool lean = weff_in && aff && (c.reserved & PM_COLS_ALL_UNIFORM_AREA) != 0;
-      static const int lean_d = []() {
-        const char *e = getenv("PYMOC_STREAM_LEAN_D");  // experiments: ring depth of the lean form
-        return e ? atoi(e) : 0;
-      }();
-      if (lean && lean_d == 4)
-        hipLaunchKernelGGL((k_column_stream<P, 4, true, true>), dim3((waves + 3) / 4), dim3(256), 0,
-                           st, c, wA, dt, nsteps, cpw, dt_ok, weff_in);
-      else if (lean && lean_d == 5)
-        hipLaunchKernelGGL((k_column_stream<P, 5, true, true>), dim3((waves + 3) / 4), dim3(256), 0,
-                           st, c, wA, dt, nsteps, cpw, dt_ok, weff_in);
-      else if (lean && lean_d == 8)
-        hipLaunchKernelGGL((k_column_stream<P, 8, true, true>), dim3((waves + 3) / 4), dim3(256), 0,
-                           st, c, wA, dt, nsteps, cpw, dt_ok, weff_in);
-      else if (lean && lean_d == 6)
-        hipLaunchKernelGGL((k_column_stream<P, 6, true, true>), dim3((waves + 3) / 4), dim3(256), 0,
-                           st, c, wA, dt, nsteps, cpw, dt_ok, weff_in);
-      else if (lean) {
-        // measured at 262144 columns x nz = 100 (profiles/r04/probe_stream_lean.py): ring depth
-        // 4 / 5 / 6 / 8 -> 150.5 / 148.8 / 158.6 / 154.8 us at their best columns-per-wave; 16
-        // columns per wave beat 32 (the non-lean forms' choice) and 8
-        int cl = cpw;
-        if (!getenv("PYMOC_STREAM_CPW")) {
-          cl = c.ncols / 16384;
-          cl = cl < 2 ? 2 : (cl > 16 ? 16 : cl);
-        }
-        unsigned wl = (unsigned)((c.ncols + cl - 1) / cl);
-        bool vec = false;
-        if constexpr (P == 2)
-          vec = (c.nz & 1) == 0 && ((((unsigned long long)c.b) | ((unsigned long long)wA)) & 15ull) == 0ull &&
-                !getenv("PYMOC_STREAM_NO_VEC");
-        const bool d3 = (c.reserved & PM_COLS_DIV3_PROVEN) != 0;
-        // every wave exactly 8 columns: the straight-line instantiation (CPWU).  Measured at 262144
-        // columns (profiles/r05/stream_variants.log): ring depth 3 / 4 / 5 / 6 at 16 columns per wave
-        // 132 / 133 / 133 / 134 us -- with a ring that works its depth no longer matters -- and depth
-        // 5 at 8 / 16 / 32 columns per wave 127 / 133 / 268 us
-        const bool u16 = vec && c.ncols % 8 == 0 && c.ncols >= 8 * 4096 &&
-                         !getenv("PYMOC_STREAM_LOOP") && !getenv("PYMOC_STREAM_CPW");
-        if (u16) {
-          cl = 8;
-          wl = (unsigned)(c.ncols / 8);
-        }
-#ifdef PM_STREAM_VARIANTS  // experiments (profiles/r05/stream_variants.sh): ring depth x columns per wave
-        if constexpr (P == 2) {
-          const char *ev = getenv("PYMOC_STREAM_VARIANT");
-          if (ev && vec && d3) {
-            const int dv = atoi(ev), cv = strchr(ev, ',') ? atoi(strchr(ev, ',') + 1) : 16;
-            const unsigned wv = (unsigned)((c.ncols + cv - 1) / cv);
-#define PM_SV(DD, CC)                                                                              \
-  if (dv == DD && cv == CC && c.ncols % CC == 0) {                                                 \
-    hipLaunchKernelGGL((k_column_stream<P, DD, true, true, true, true, CC>), dim3((wv + 3) / 4),   \
-                       dim3(256), 0, st, c, wA, dt, nsteps, cv, dt_ok, weff_in);                   \
-    PM_HIP(hipGetLastError());                                                                     \
-    return PM_OK;                                                                                  \
-  }
-            PM_SV(4, 16) PM_SV(6, 16) PM_SV(5, 32) PM_SV(5, 8) PM_SV(3, 16)
-#undef PM_SV
-          }
-        }
-#endif
-        if constexpr (P == 2) {
-          if (vec && u16 && d3)
-            hipLaunchKernelGGL((k_column_stream<P, 5, true, true, true, true, 8>), dim3((wl + 3) / 4),
-                               dim3(256), 0, st, c, wA, dt, nsteps, cl, dt_ok, weff_in);
-          else if (vec && u16)
-            hipLaunchKernelGGL((k_column_stream<P, 5, true, true, true, false, 8>), dim3((wl + 3) / 4),
-                               dim3(256), 0, st, c, wA, dt, nsteps, cl, dt_ok, weff_in);
-          else if (vec && d3)
-            hipLaunchKernelGGL((k_column_stream<P, 5, true, true, true, true>), dim3((wl + 3) / 4),
-                               dim3(256), 0, st, c, wA, dt, nsteps, cl, dt_ok, weff_in);
-          else if (vec)
-            hipLaunchKernelGGL((k_column_stream<P, 5, true, true, true>), dim3((wl + 3) / 4), dim3(256),
-                               0, st, c, wA, dt, nsteps, cl, dt_ok, weff_in);
-        }
-        if (!vec)
-          hipLaunchKernelGGL((k_column_stream<P, 5, true, true>), dim3((wl + 3) / 4), dim3(256), 0,
-                             st, c, wA, dt, nsteps, cl, dt_ok, weff_in);
-      }
-      else if (P == 2 && !aff && c.ncols % 8 == 0 && c.ncols >= 8 * 4096 && !getenv("PYMOC_STREAM_LOOP") &&
-               !getenv("PYMOC_STREAM_CPW") &&
-               ((weff_in && (c.reserved & PM_COLS_ALL_UNIFORM_AREA)) ||
-                (!weff_in && !(c.reserved & PM_COLS_ALL_UNIFORM_AREA)))) {
-        // the straight-line forms of the two other regimes the bench reports: forcing precombined
-        // and every Area one number (32 nz B per column-step), and the C-ABI default (48 nz B)
-        const unsigned w8 = (unsigned)(c.ncols / 8);
-        if constexpr (P == 2) {
-          if (weff_in)
-            hipLaunchKernelGGL((k_column_stream<P, 3, false, false, false, false, 8, 1, 1>),
-                               dim3((w8 + 3) / 4), dim3(256), 0, st, c, wA, dt, nsteps, 8, dt_ok, weff_in);
-          else
-            hipLaunchKernelGGL((k_column_stream<P, 2, false, false, false, false, 8, 0, 0>),
-                               dim3((w8 + 3) / 4), dim3(256), 0, st, c, wA, dt, nsteps, 8, dt_ok, weff_in);
-        }
-      }
-      else if (weff_in && aff)
-        hipLaunchKernelGGL((k_column_stream<P, 4, true>), dim3((waves + 3) / 4), dim3(256), 0, st, c,
-                           wA, dt, nsteps, cpw, dt_ok, weff_in);
-      else if (weff_in)
-        hipLaunchKernelGGL((k_column_stream<P, 3>), dim3((waves + 3) / 4), dim3(256), 0, st, c, wA,
-                           dt, nsteps, cpw, dt_ok, weff_in);
-      else if (aff)
-        hipLaunchKernelGGL((k_column_stream<P, 3, true>), dim3((waves + 3) / 4), dim3(256), 0, st, c,
-                           wA, dt, nsteps, cpw, dt_ok, weff_in);
-      else
-        hipLaunchKernelGGL((k_column_stream<P, 2>), dim3((waves + 3) / 4), dim3(256), 0, st, c, wA,
-                           dt, nsteps, cpw, dt_ok, weff_in);
-      PM_HIP(hipGetLastError());
-      return PM_OK;
+      pl.kernel = weff ? (aff ? CK_STREAM_WEFF_AFF : CK_STREAM_WEFF) : (aff ? CK_STREAM_AFF : CK_STREAM);
     }
+    const unsigned waves = (unsigned)((c.ncols + pl.cpw - 1) / pl.cpw);
+    pl.grid = (waves + 3) / 4;
+  } else if (nsteps >= 3 && plain) {
+    // the reciprocal path pays 3 true divisions per level up front: worth it from 3 steps on
+    if (wave_per_col && (ops & PM_OP_CONTRACTED))
+      pl.kernel = CK_STEPS_CONTRACTED;
+    else if (wave_per_col && ua)
+      pl.kernel = d3 ? CK_STEPS_DIV3_UA : CK_STEPS_PLAIN_UA;
+    else
+      pl.kernel = CK_STEPS_PLAIN;
+  } else if (nsteps >= 3) {
+    pl.kernel = CK_STEPS_RECIP;
   }
-  if constexpr (G == 64 && P <= 4) {
-    if (contracted && nsteps >= 3 && ops == PM_OP_TIMESTEP && !vdx) {
-      hipLaunchKernelGGL((k_column_steps<G, P, 4, true>), dim3(grid), dim3(256), 0, st, c, wA, vk,
-                         bin, dt, nsteps, ops | (weff_in ? PM_OP_WEFF : 0) | wa_psi);
-      PM_HIP(hipGetLastError());
-      return PM_OK;
-    }
-  }
-  // the reciprocal path pays 3 true divisions per level up front: worth it from 3 steps on
-  bool launched = false;
-  if constexpr (G == 64 && P <= 4) {
-    if (nsteps >= 3 && ops == PM_OP_TIMESTEP && !vdx && (c.reserved & PM_COLS_ALL_UNIFORM_AREA)) {
-      static const int lds_pad = []() {
-        const char *e = getenv("PYMOC_K1_LDS");  // experiments: unused LDS per block caps the occupancy
-        return e ? atoi(e) : 0;
-      }();
-      if ((c.reserved & PM_COLS_DIV3_PROVEN) != 0)  // (the caller's pm_div3_proven verdict)
-        hipLaunchKernelGGL((k_column_steps<G, P, 6, true, true>), dim3(grid), dim3(256), lds_pad, st, c, wA,
-                           vk, bin, dt, nsteps, ops | (weff_in ? PM_OP_WEFF : 0) | wa_psi);
-      else
-        hipLaunchKernelGGL((k_column_steps<G, P, 2, true, true>), dim3(grid), dim3(256), lds_pad, st, c, wA,
-                           vk, bin, dt, nsteps, ops | (weff_in ? PM_OP_WEFF : 0) | wa_psi);
-      launched = true;
-    }
-  }
-  if (launched) {
-  } else if (nsteps >= 3 && ops == PM_OP_TIMESTEP && !vdx)
-    hipLaunchKernelGGL((k_column_steps<G, P, 2, true>), dim3(grid), dim3(256), 0, st, c, wA,
-                       vk, bin, dt, nsteps, ops | (weff_in ? PM_OP_WEFF : 0) | wa_psi);
-  else if (nsteps >= 3)
-    hipLaunchKernelGGL((k_column_steps<G, P, 1, false>), dim3(grid), dim3(256), 0, st, c, wA,
-                       vdx, bin, dt, nsteps, ops | (weff_in ? PM_OP_WEFF : 0));
+  return pl;
+}
+
+// The planned kernel's name as profilers report it -- no namespace, no spaces, every template
+// argument written out -- which keys profiles/*/counters.json.  "" for CK_NONE.
+inline int column_kernel_name(const ColumnPlan &pl, char *name, size_t len) {
+  const ColKernel k = col_kernel(pl.kernel);
+  auto tf = [](bool v) { return v ? "true" : "false"; };
+  int n = 0;
+  if (pl.kernel == CK_NONE)
+    n = snprintf(name, len, "%s", "");
+  else if (k.stream)
+    n = snprintf(name, len, "k_column_stream<%d,%d,%s,%s,%s,%s,%d,%d,%d>", pl.P, k.d, tf(k.aff),
+                 tf(k.lean), tf(k.vec), tf(k.d3), k.cpwu, k.wefft, k.uabt);
   else
-    hipLaunchKernelGGL((k_column_steps<G, P, 0, false>), dim3(grid), dim3(256), 0, st, c,
-                       wA, vdx, bin, dt, nsteps, ops | (weff_in ? PM_OP_WEFF : 0));
+    n = snprintf(name, len, "k_column_steps<%d,%d,%d,%s,%s>", pl.G, pl.P, k.fast, tf(k.plain),
+                 tf(k.ua));
+  PM_REQUIRE(n >= 0 && (size_t)n < len, "name buffer of %zu bytes too small", len);
+  return PM_OK;
+}
+
+template <int G, int P, ColKernelId K>
+int launch_column_kernel(const ColumnPlan &pl, const pm_columns &c, const double *wA,
+                         const double *vdx, const double *bin, double dt, int nsteps, int ops,
+                         hipStream_t st) {
+  constexpr ColKernel k = col_kernel(K);
+  if constexpr (!k.compiled(G, P)) {
+    return fail(PM_EINVAL, "column kernel %d is not compiled for G=%d P=%d", (int)K, G, P);
+  } else if constexpr (k.stream) {
+    // dt inside the exact-division window (in_fast_div_range, host side)
+    const double adt = dt < 0 ? -dt : dt;
+    const bool dt_ok = dt == 0.0 || (adt >= 0x1p-200 && adt <= 0x1p200);
+    hipLaunchKernelGGL((k_column_stream<P, k.d, k.aff, k.lean, k.vec, k.d3, k.cpwu, k.wefft, k.uabt>),
+                       dim3(pl.grid), dim3(256), 0, st, c, wA, dt, nsteps, pl.cpw, dt_ok,
+                       (ops & PM_OP_WEFF) != 0);
+  } else {
+    // (PM_OP_CONTRACTED selected the instantiation; PM_OP_WA_TWOBASIN's third array is in vdx)
+    hipLaunchKernelGGL((k_column_steps<G, P, k.fast, k.plain, k.ua>), dim3(pl.grid), dim3(256), 0,
+                       st, c, wA, vdx, bin, dt, nsteps, ops & ~PM_OP_CONTRACTED);
+  }
   PM_HIP(hipGetLastError());
   return PM_OK;
 }
 
-int column_steps_g16(int P, const pm_columns &c, const double *wA, const double *vdx,
-                     const double *bin, double dt, int nsteps, int ops, hipStream_t st);
-int column_steps_g32(int P, const pm_columns &c, const double *wA, const double *vdx,
-                     const double *bin, double dt, int nsteps, int ops, hipStream_t st);
-int column_steps_g64(int P, const pm_columns &c, const double *wA, const double *vdx,
-                     const double *bin, double dt, int nsteps, int ops, hipStream_t st);
-
-inline int auto_lanes_per_col(int ncols, int nz) {
-  // Few columns: one wave per column keeps every SIMD busy (1024 SIMDs on the chip).
-  // Many columns: narrower groups raise per-lane ILP and cut idle padding lanes.
-  // measured on MI355X (profiles/r01_sweep_columns.txt): one wave per column wins at every
-  // ensemble size from 1024 to 65536 columns at nz=100
-  (void)ncols;
-  int G = 64;
-  while (G < 64 && pick_levels_per_lane(G, (nz + G - 1) / G) < 0) G *= 2;
-  return G;
+template <int G, int P>
+int launch_column_steps(const ColumnPlan &pl, const pm_columns &c, const double *wA,
+                        const double *vdx, const double *bin, double dt, int nsteps, int ops,
+                        hipStream_t st) {
+#define PM_CK_LAUNCH(id, args) \
+  case id: return launch_column_kernel<G, P, id>(pl, c, wA, vdx, bin, dt, nsteps, ops, st);
+  switch (pl.kernel) {
+    PM_COLUMN_KERNELS(PM_CK_LAUNCH)
+    default: return PM_OK;  // CK_NONE
+  }
+#undef PM_CK_LAUNCH
 }
+
+int column_steps_g16(const ColumnPlan &pl, const pm_columns &c, const double *wA,
+                     const double *vdx, const double *bin, double dt, int nsteps, int ops,
+                     hipStream_t st);
+int column_steps_g32(const ColumnPlan &pl, const pm_columns &c, const double *wA,
+                     const double *vdx, const double *bin, double dt, int nsteps, int ops,
+                     hipStream_t st);
+int column_steps_g64(const ColumnPlan &pl, const pm_columns &c, const double *wA,
+                     const double *vdx, const double *bin, double dt, int nsteps, int ops,
+                     hipStream_t st);
 
 }  // namespace pm

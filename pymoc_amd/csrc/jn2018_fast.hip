@@ -1848,11 +1848,10 @@ static int launch_fast(const pm_jn2018 &a, double dt, int nsteps, hipStream_t st
                    al(a.cols.dAkappa) && al(a.wA) && al(a.Psi_SO);
   const bool ct = (a.hints & PM_JN_CONTRACTED) != 0;
   // round 5: both columns of a member side by side in the wave's two halves (k_jn2018_split).
-  // Opt-in (PM_JN_SPLIT_LANES, or PYMOC_JN_SPLIT=1 for A/B runs): 7 % fewer vector instructions
-  // per launch, measured a tie on config 5; shapes 65..128 and 193..224
-  static const bool env_split = getenv("PYMOC_JN_SPLIT") != nullptr;
+  // Opt-in (PM_JN_SPLIT_LANES): 7 % fewer vector instructions per launch, measured a tie on
+  // config 5; shapes 65..128 and 193..224
   const int PS = (a.cols.nz + 31) / 32;
-  const bool split = ((a.hints & PM_JN_SPLIT_LANES) || env_split) && (PS == 3 || PS == 4 || PS == 7);
+  const bool split = (a.hints & PM_JN_SPLIT_LANES) && (PS == 3 || PS == 4 || PS == 7);
   if (split) {
     // 16-byte row accesses: every row starts 16-byte aligned and holds an even number of levels
     const bool v2 = a.cols.nz % 2 == 0 && al(a.cols.b) && al(a.cols.area) && al(a.cols.kappa) &&

@@ -497,8 +497,10 @@ int pm_graph_destroy(pm_graph_t graph) {
 }
 
 // -------------------------------------------------------------------- Column
-static int column_shape(int ncols, int nz, int lanes_per_col, int *G_out, int *P_out) {
-  int G = lanes_per_col ? lanes_per_col : auto_lanes_per_col(ncols, nz);
+static int column_shape(int nz, int lanes_per_col, int *G_out, int *P_out) {
+  // lanes_per_col = 0: one wave per column, measured on MI355X (profiles/r01_sweep_columns.txt)
+  // to win at every ensemble size from 1024 to 65536 columns at nz=100
+  int G = lanes_per_col ? lanes_per_col : 64;
   PM_REQUIRE(G == 16 || G == 32 || G == 64, "lanes_per_col must be 0, 16, 32 or 64");
   int P = pick_levels_per_lane(G, (nz + G - 1) / G);
   while (P < 0 && G < 64) {
@@ -515,36 +517,14 @@ int pm_column_kernel_shape(int32_t ncols, int32_t nz, int32_t lanes_per_col, int
                            int32_t *levels_per_lane) {
   PM_REQUIRE(lanes && levels_per_lane, "NULL output");
   PM_REQUIRE(nz >= 2 && nz <= 1024, "nz must be in [2,1024]");
-  int G = 0, P = 0;
-  const int rc = column_shape(ncols, nz, lanes_per_col, &G, &P);
-  if (rc != PM_OK) return rc;
-  *lanes = G;
-  *levels_per_lane = P;
-  return PM_OK;
+  return column_shape(nz, lanes_per_col, lanes, levels_per_lane);
 }
 
-int pm_column_kernel_name(int32_t ncols, int32_t nz, int32_t lanes_per_col, int32_t nsteps,
-                          int32_t ops, int32_t has_horadv, char *name, size_t name_len) {
-  PM_REQUIRE(name && name_len > 0, "NULL output");
-  PM_REQUIRE(nz >= 2 && nz <= 1024, "nz must be in [2,1024]");
-  int G = 0, P = 0;
-  const int rc = column_shape(ncols, nz, lanes_per_col, &G, &P);
-  if (rc != PM_OK) return rc;
-  const bool plain =
-      (ops & ~(PM_OP_WEFF | PM_OP_CONTRACTED | PM_OP_WA_PSI | PM_OP_WA_TWOBASIN)) == PM_OP_TIMESTEP && !has_horadv;
-  if (G == 64 && P <= 4 && nsteps < 3 && plain && stream_cols_per_wave(ncols) >= 2)
-    snprintf(name, name_len, "k_column_stream<%d>", P);  // (+ ring depth / affine-kappa variants)
-  else if (G == 64 && P <= 4 && nsteps >= 3 && plain && (ops & PM_OP_CONTRACTED))
-    snprintf(name, name_len, "k_column_steps<64,%d,4,true>", P);
-  else  // mirrors launch_column_steps (column.hip.h)
-    snprintf(name, name_len, "k_column_steps<%d,%d,%d,%s>", G, P,
-             nsteps >= 3 ? (plain ? 2 : 1) : 0, (nsteps >= 3 && plain) ? "true" : "false");
-  return PM_OK;
-}
-
-int pm_column_steps(const pm_columns *cols, const double *wA, const double *vdx_in,
-                    const double *b_in, double dt, int32_t nsteps, int32_t ops,
-                    int32_t lanes_per_col, pm_stream_t stream) {
+// The argument checks of pm_column_steps (but b_in's) and the launch the call makes
+// (pl->kernel = CK_NONE: nothing to launch).
+static int column_call(const pm_columns *cols, const double *wA, const double *vdx_in,
+                       int32_t nsteps, int32_t ops, int32_t lanes_per_col, ColumnPlan *pl) {
+  *pl = ColumnPlan{CK_NONE, 0, 0, 0, 0};
   PM_REQUIRE(cols, "cols is NULL");
   const pm_columns &c = *cols;
   PM_REQUIRE(c.ncols >= 0 && c.nz >= 2 && c.nz <= 1024,
@@ -557,7 +537,7 @@ int pm_column_steps(const pm_columns *cols, const double *wA, const double *vdx_
   PM_REQUIRE((ops & ~(PM_OP_TIMESTEP | PM_OP_WEFF | PM_OP_CONTRACTED | PM_OP_WA_PSI | PM_OP_WA_TWOBASIN)) == 0,
              "unknown op bits 0x%x", ops);
   if (ops & PM_OP_WA_TWOBASIN) {
-    PM_REQUIRE(vdx_in && b_in && !(ops & (PM_OP_WEFF | PM_OP_WA_PSI)) &&
+    PM_REQUIRE(vdx_in && !(ops & (PM_OP_WEFF | PM_OP_WA_PSI)) &&
                    (ops & PM_OP_TIMESTEP) == PM_OP_TIMESTEP && nsteps >= 3 && c.ncols % 3 == 0,
                "PM_OP_WA_TWOBASIN: plain timesteps (>= 3 per launch) of a three-column ensemble, the "
                "three overturning arrays given, no PM_OP_WEFF / PM_OP_WA_PSI");
@@ -566,20 +546,39 @@ int pm_column_steps(const pm_columns *cols, const double *wA, const double *vdx_
                    nsteps >= 3 && (c.ncols & 1) == 0,
                "PM_OP_WA_PSI: plain timesteps (>= 3 per launch) of a two-column ensemble, no "
                "horadv, no PM_OP_WEFF");
-    vdx_in = nullptr;
-  } else {
-    PM_REQUIRE(!vdx_in || b_in, "b_in is needed if vdx_in is provided");
   }
   PM_REQUIRE(!(ops & PM_OP_VERTADVDIFF) || wA, "wA is NULL");
-  if (c.ncols == 0 || nsteps == 0 || (ops & PM_OP_TIMESTEP) == 0) return PM_OK;
+  if (nsteps == 0 || (ops & PM_OP_TIMESTEP) == 0) return PM_OK;
   int G = 0, P = 0;
-  const int src = column_shape(c.ncols, c.nz, lanes_per_col, &G, &P);
-  if (src != PM_OK) return src;
+  const int rc = column_shape(c.nz, lanes_per_col, &G, &P);
+  if (rc != PM_OK) return rc;
+  *pl = column_plan(c, wA, vdx_in, nsteps, ops, G, P);
+  return PM_OK;
+}
+
+int pm_column_kernel_name(const pm_columns *cols, const double *wA, const double *vdx_in,
+                          int32_t nsteps, int32_t ops, int32_t lanes_per_col, char *name,
+                          size_t name_len) {
+  PM_REQUIRE(name && name_len > 0, "NULL output");
+  ColumnPlan pl;
+  const int rc = column_call(cols, wA, vdx_in, nsteps, ops, lanes_per_col, &pl);
+  if (rc != PM_OK) return rc;
+  return column_kernel_name(pl, name, name_len);
+}
+
+int pm_column_steps(const pm_columns *cols, const double *wA, const double *vdx_in,
+                    const double *b_in, double dt, int32_t nsteps, int32_t ops,
+                    int32_t lanes_per_col, pm_stream_t stream) {
+  ColumnPlan pl;
+  const int rc = column_call(cols, wA, vdx_in, nsteps, ops, lanes_per_col, &pl);
+  if (rc != PM_OK) return rc;
+  PM_REQUIRE(!vdx_in || b_in || cols->ncols == 0, "b_in is needed if vdx_in is provided");
+  if (pl.kernel == CK_NONE) return PM_OK;
   hipStream_t st = resolve_stream(stream);
-  switch (G) {
-    case 16: return column_steps_g16(P, c, wA, vdx_in, b_in, dt, nsteps, ops, st);
-    case 32: return column_steps_g32(P, c, wA, vdx_in, b_in, dt, nsteps, ops, st);
-    default: return column_steps_g64(P, c, wA, vdx_in, b_in, dt, nsteps, ops, st);
+  switch (pl.G) {
+    case 16: return column_steps_g16(pl, *cols, wA, vdx_in, b_in, dt, nsteps, ops, st);
+    case 32: return column_steps_g32(pl, *cols, wA, vdx_in, b_in, dt, nsteps, ops, st);
+    default: return column_steps_g64(pl, *cols, wA, vdx_in, b_in, dt, nsteps, ops, st);
   }
 }
 
@@ -692,8 +691,7 @@ int pm_jn2018_steps(const pm_jn2018 *jn, double dt, int32_t nsteps, pm_stream_t 
   PM_REQUIRE(nsteps >= 0, "nsteps < 0");
   if (a.n == 0 || nsteps == 0) return PM_OK;
   hipStream_t st = resolve_stream(stream);
-  const bool force_general = getenv("PYMOC_JN_GENERAL") != nullptr;  // A/B experiments
-  if (!force_general && jn2018_fast_applies(a)) return launch_jn2018_fast(a, dt, nsteps, st);
+  if (jn2018_fast_applies(a)) return launch_jn2018_fast(a, dt, nsteps, st);
   switch ((c.nz + 63) / 64) {
     case 1: return launch_jn2018_steps<1>(a, dt, nsteps, st);
     case 2: return launch_jn2018_steps<2>(a, dt, nsteps, st);

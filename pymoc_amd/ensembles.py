@@ -209,8 +209,7 @@ class TwoColEnsemble(object):
     self._overlap = self.so is not None and bool(overlap_updates)
     if self._overlap:
       from .device import Stream, Event
-      import os
-      self._side = Stream(high_priority=os.environ.get("PYMOC_SIDE_PRIORITY", "0") == "1")
+      self._side = Stream()
       self._ev_fork, self._ev_join = Event(), Event()
     can_fuse = (self.so is None and arith == "exact" and self.cols.uniform_area and
                 not self.cols.has_bzbot and

@@ -304,7 +304,8 @@ def test_operands_outside_the_fast_division_window_streaming_kernel(gpu):
   b0[sel], wA[sel], bs[sel], bbot[sel] = b0s, wAs, bss, bbots
   batch = gpu.ColumnBatch(c["z"], c["kappa"], c["Area"], b0, bs=bs, bbot=bbot, N2min=c["N2min"],
                           do_conv=c["do_conv"])
-  assert batch.kernel_name(1).startswith("k_column_stream")
+  assert batch.uniform_area  # (every Area one number without the forcing precombined: not straight-line)
+  assert batch.kernel_name(1) == batch.kernel_name(2) == "k_column_stream<2,2,false,false,false,false,0,-1,-1>"
   with np.errstate(all="ignore"):
     batch.steps(wA, c["dt"], 1)
     batch.steps(wA, c["dt"], 2)
@@ -336,10 +337,14 @@ def test_lean_streaming_forms_bitwise_with_operands_outside_the_window(gpu, nz):
   b0[sel], wA[sel], bs[sel], bbot[sel] = b0s, wAs, bss, bbots
   aff = gpu.ColumnBatch(c["z"], c["kappa"], c["Area"], b0, bs=bs, bbot=bbot, N2min=c["N2min"],
                         do_conv=c["do_conv"], kappa_affine=(c["kappa_back"], c["kappa_profile"]))
-  assert aff.kappa_base is not None
-  assert aff.kernel_name(1).startswith("k_column_stream")
+  assert aff.kappa_base is not None and aff.uniform_area
   with np.errstate(all="ignore"):
     w = aff.combine_forcing(gpu.DeviceArray.from_host(wA))
+    P = {100: 2, 81: 2, 40: 1, 128: 2, 150: 3}[nz]
+    vec = P == 2 and nz % 2 == 0  # (16-byte accesses; 8 columns per wave need 8 | N)
+    tf = lambda v: "true" if v else "false"  # noqa: E731
+    assert aff.kernel_name(1, precombined=True, wA=w) == "k_column_stream<%d,5,true,true,%s,%s,0,-1,-1>" % (
+        P, tf(vec), tf(vec and aff.div3_proven))
     weff_host = w.download()
     for _ in range(3):
       aff.steps(w, c["dt"], 1, precombined=True)
@@ -405,7 +410,8 @@ def test_three_instruction_quotient_hint_bitwise(gpu, nsteps):
   fast, base = make(), make()
   assert fast.div3_proven
   base.use_hints(div3=False)
-  assert ",6,true,true>" in fast.kernel_name(nsteps) and ",2,true,true>" in base.kernel_name(nsteps)
+  assert fast.kernel_name(nsteps) == "k_column_steps<64,2,6,true,true>"
+  assert base.kernel_name(nsteps) == "k_column_steps<64,2,2,true,true>"
   wA = gpu.DeviceArray.from_host(c["wA"])
   fast.steps(wA, c["dt"], nsteps)
   base.steps(wA, c["dt"], nsteps)
@@ -464,11 +470,12 @@ def _rel(a, ref):
   return np.max(np.abs(a - ref)) / np.max(np.abs(ref))
 
 
-def test_contracted_mode_vs_reference_goldens(gpu):
+def test_contracted_mode_kernel_and_reference_goldens(gpu):
   """The contracted update b_i += cu_i (b_{i+1}-b_i) + cl_i (b_i-b_{i-1}) against the
   reference's own numbers: every G1 single-column case over 3 steps (uniform / non-uniform
   grids, convective adjustment, bottom-stratification BC), and the G8 / G17 config-2 members
-  over 200 and over the whole 1000 steps -- within 1e-12; the default mode stays bit-identical."""
+  over 200 and over the whole 1000 steps -- within 1e-12; the default mode stays bit-identical.
+  Each G1 case up to nz = 256 runs the contracted instantiation, named in full."""
   g = load_golden("column_steps")
   worst = 0.
   for k in range(int(g["ncases"])):
@@ -479,7 +486,9 @@ def test_contracted_mode_vs_reference_goldens(gpu):
     batch = gpu.ColumnBatch(g[p + "z"], g[p + "kappa"], g[p + "Area"], g[p + "b0"], bs=bs,
                             bbot=bbot, bzbot=None if np.isnan(bzbot) else bzbot,
                             N2min=N2min, do_conv=bool(do_conv))
-    assert batch.kernel_name(3, arith="contracted").endswith(",4,true>") or g[p + "z"].size > 256
+    _, P = batch.kernel_shape()
+    assert (batch.kernel_name(3, arith="contracted") == "k_column_steps<64,%d,4,true,false>" % P or
+            g[p + "z"].size > 256)
     batch.steps(g[p + "wA"], dt, 3, arith="contracted")
     worst = max(worst, _rel(batch.get_b()[0], g[p + "b3"]))
   assert worst <= CONTRACTED_RTOL, worst

@@ -102,6 +102,121 @@ def test_cabi_rejects_bad_arguments_before_touching_the_device():
   assert L.pm_equi_column_scratch_doubles(64) >= 64 * 100
 
 
+def test_column_kernel_name_follows_the_launch_plan():
+  """pm_column_kernel_name names the instantiation pm_column_steps launches, read off the call
+  alone: one case per row of the launch plan (column.hip.h, column_plan) and both sides of each
+  gate, spelled as rocprofv3 reports it.  The stand-in pointers are never dereferenced."""
+  from pymoc_amd import _lib
+  L, C = _lib.lib, ctypes
+  A, M = 0x10000, 0x10008  # 16-byte aligned / misaligned addresses
+  T, WEFF, CT = _lib.PM_OP_TIMESTEP, _lib.PM_OP_WEFF, _lib.PM_OP_CONTRACTED
+  PSI, TWO = _lib.PM_OP_WA_PSI, _lib.PM_OP_WA_TWOBASIN
+
+  def name(ncols=32768, nz=100, nsteps=1, ops=T, ua=False, d3=False, aff=False, b=A, wA=A,
+           vdx=None, lanes=0):
+    c = _lib.pm_columns()
+    c.ncols, c.nz, c.nsel = ncols, nz, 1
+    c.reserved = (_lib.PM_COLS_ALL_UNIFORM_AREA if ua else 0) | (_lib.PM_COLS_DIV3_PROVEN if d3 else 0)
+    c.z = c.kappa = c.area = c.dAkappa = c.bs = c.bbot = c.N2min = A
+    c.b = b
+    if aff:
+      c.kappa_base = c.kappa_profile = A
+    buf = C.create_string_buffer(96)
+    rc = L.pm_column_kernel_name(C.byref(c), wA, vdx, nsteps, ops, lanes, buf, 96)
+    assert rc == _lib.PM_OK, L.pm_last_error()
+    return buf.value.decode()
+
+  lean = dict(ops=T | WEFF, aff=True, ua=True)
+  S = "k_column_stream<%s>"
+  cases = [
+      # one wave per column, P <= 4, 1-2 plain steps, >= 16384 columns: the streaming kernel;
+      # lean (PM_OP_WEFF, affine kappa, every Area one number) with 16-byte accesses
+      (dict(lean, d3=True), S % "2,5,true,true,true,true,8,-1,-1"),
+      (dict(lean, nsteps=2), S % "2,5,true,true,true,false,8,-1,-1"),
+      (dict(lean, d3=True, ncols=32760), S % "2,5,true,true,true,true,0,-1,-1"),
+      (dict(lean, ncols=32772), S % "2,5,true,true,true,false,0,-1,-1"),
+      (dict(lean, ncols=16384), S % "2,5,true,true,true,false,0,-1,-1"),
+      (dict(lean, ncols=16383), "k_column_steps<64,2,0,false,false>"),
+      (dict(lean, nsteps=3), "k_column_steps<64,2,2,true,true>"),
+      # ... without them: nz odd, b or the forcing misaligned, P != 2 (PM_COLS_DIV3_PROVEN unused)
+      (dict(lean, d3=True, nz=99), S % "2,5,true,true,false,false,0,-1,-1"),
+      (dict(lean, d3=True, b=M), S % "2,5,true,true,false,false,0,-1,-1"),
+      (dict(lean, d3=True, wA=M), S % "2,5,true,true,false,false,0,-1,-1"),
+      (dict(lean, d3=True, nz=64), S % "1,5,true,true,false,false,0,-1,-1"),
+      (dict(lean, nz=150), S % "3,5,true,true,false,false,0,-1,-1"),
+      (dict(lean, nz=256), S % "4,5,true,true,false,false,0,-1,-1"),
+      (dict(lean, nz=257), "k_column_steps<64,5,0,false,false>"),
+      (dict(lean, lanes=32), "k_column_steps<32,4,0,false,false>"),
+      # straight-line forms: P = 2, no affine kappa, 8 | ncols >= 32768, PM_OP_WEFF == every Area one number
+      (dict(), S % "2,2,false,false,false,false,8,0,0"),
+      (dict(b=M, wA=M), S % "2,2,false,false,false,false,8,0,0"),
+      (dict(ops=T | WEFF, ua=True), S % "2,3,false,false,false,false,8,1,1"),
+      (dict(ops=T | WEFF, ua=True, d3=True), S % "2,3,false,false,false,false,8,1,1"),
+      (dict(ncols=32760), S % "2,2,false,false,false,false,0,-1,-1"),
+      (dict(ncols=32772), S % "2,2,false,false,false,false,0,-1,-1"),
+      (dict(nz=64), S % "1,2,false,false,false,false,0,-1,-1"),
+      # the other streaming forms
+      (dict(ua=True), S % "2,2,false,false,false,false,0,-1,-1"),
+      (dict(ops=T | WEFF), S % "2,3,false,false,false,false,0,-1,-1"),
+      (dict(aff=True), S % "2,3,true,false,false,false,0,-1,-1"),
+      (dict(aff=True, ua=True), S % "2,3,true,false,false,false,0,-1,-1"),
+      (dict(ops=T | WEFF, aff=True), S % "2,4,true,false,false,false,0,-1,-1"),
+      (dict(ops=T | CT, ncols=16384), S % "2,2,false,false,false,false,0,-1,-1"),
+      (dict(ops=T | WEFF, ncols=16384, nz=200), S % "4,3,false,false,false,false,0,-1,-1"),
+      # not a plain timestep: horadv, part of the step
+      (dict(vdx=A), "k_column_steps<64,2,0,false,false>"),
+      (dict(ops=_lib.PM_OP_CONVECT | _lib.PM_OP_VERTADVDIFF), "k_column_steps<64,2,0,false,false>"),
+      # >= 3 steps: the fused kernel
+      (dict(nsteps=3, ops=T | CT), "k_column_steps<64,2,4,true,false>"),
+      (dict(nsteps=3, ops=T | CT, ua=True, d3=True), "k_column_steps<64,2,4,true,false>"),
+      (dict(nsteps=3, ops=T | CT, lanes=32), "k_column_steps<32,4,2,true,false>"),
+      (dict(nsteps=3, ops=T | CT, nz=300), "k_column_steps<64,5,2,true,false>"),
+      (dict(nsteps=3, ops=T | CT, vdx=A), "k_column_steps<64,2,1,false,false>"),
+      (dict(nsteps=3, ua=True, d3=True), "k_column_steps<64,2,6,true,true>"),
+      (dict(nsteps=3, ua=True), "k_column_steps<64,2,2,true,true>"),
+      (dict(nsteps=3, d3=True), "k_column_steps<64,2,2,true,false>"),
+      (dict(nsteps=3, ua=True, d3=True, nz=256), "k_column_steps<64,4,6,true,true>"),
+      (dict(nsteps=3, ua=True, nz=300), "k_column_steps<64,5,2,true,false>"),
+      (dict(nsteps=3, ua=True, lanes=16), "k_column_steps<16,7,2,true,false>"),
+      (dict(nsteps=3, ops=T | WEFF, aff=True, ua=True), "k_column_steps<64,2,2,true,true>"),
+      (dict(nsteps=3), "k_column_steps<64,2,2,true,false>"),
+      (dict(nsteps=3, ops=T | PSI, ua=True, d3=True), "k_column_steps<64,2,6,true,true>"),
+      (dict(nsteps=3, ops=T | PSI, lanes=16), "k_column_steps<16,7,2,true,false>"),
+      (dict(nsteps=3, ops=T | TWO, ncols=3000, vdx=A), "k_column_steps<64,2,2,true,false>"),
+      (dict(nsteps=3, ops=T | TWO, ncols=3000, vdx=A, ua=True), "k_column_steps<64,2,2,true,true>"),
+      (dict(nsteps=3, vdx=A), "k_column_steps<64,2,1,false,false>"),
+      (dict(nsteps=3, vdx=A, ua=True), "k_column_steps<64,2,1,false,false>"),
+      (dict(nsteps=3, ops=_lib.PM_OP_VERTADVDIFF, lanes=32), "k_column_steps<32,4,1,false,false>"),
+      (dict(nsteps=2, ncols=1000, ua=True, d3=True), "k_column_steps<64,2,0,false,false>"),
+      (dict(nsteps=1, ncols=100, lanes=16, nz=10), "k_column_steps<16,1,0,false,false>"),
+      # nothing to launch
+      (dict(nsteps=0), ""),
+      (dict(ncols=0), ""),
+      (dict(ops=WEFF), ""),
+  ]
+  for kw, want in cases:
+    assert name(**kw) == want, kw
+
+  # the checks are pm_column_steps'
+  c = _lib.pm_columns()
+  c.ncols, c.nz, c.nsel = 4, 10, 1
+  buf = C.create_string_buffer(96)
+  assert L.pm_column_kernel_name(None, A, None, 1, T, 0, buf, 96) == _lib.PM_EINVAL
+  assert L.pm_column_kernel_name(C.byref(c), A, None, 1, T, 0, buf, 96) == _lib.PM_EINVAL
+  assert "NULL" in L.pm_last_error().decode()
+  c.z = c.b = c.kappa = c.area = c.dAkappa = c.bs = c.bbot = c.N2min = A
+  assert L.pm_column_kernel_name(C.byref(c), None, None, 1, T, 0, buf, 96) == _lib.PM_EINVAL
+  assert "wA" in L.pm_last_error().decode()
+  assert L.pm_column_kernel_name(C.byref(c), A, None, 1, 128, 0, buf, 96) == _lib.PM_EINVAL
+  assert L.pm_column_kernel_name(C.byref(c), A, None, 1, T | PSI, 0, buf, 96) == _lib.PM_EINVAL
+  assert L.pm_column_kernel_name(C.byref(c), A, None, 3, T | TWO, 0, buf, 96) == _lib.PM_EINVAL
+  assert L.pm_column_kernel_name(C.byref(c), A, None, 1, T, 8, buf, 96) == _lib.PM_EINVAL
+  assert L.pm_column_kernel_name(C.byref(c), A, None, 1, T, 0, None, 96) == _lib.PM_EINVAL
+  assert L.pm_column_kernel_name(C.byref(c), A, None, 1, T, 0, buf, 8) == _lib.PM_EINVAL
+  assert L.pm_column_kernel_name(C.byref(c), A, None, 1, T, 0, buf, 96) == _lib.PM_OK
+  assert buf.value == b"k_column_steps<64,1,0,false,false>"
+
+
 def test_product_does_not_import_oracle():
   pkg = os.path.join(ROOT, "pymoc_amd")
   for dirpath, _, files in os.walk(pkg):
