@@ -304,6 +304,9 @@ int pm_thermwind_residuals(int32_t m, const double *x, const double *y0, const d
 #define PM_SO_HAS_HTAPERTOP 16
 #define PM_SO_HAS_HTAPERBOT 32
 #define PM_SO_TAU_ARRAY 64     /* tau is [n][ny] on y instead of one scalar per member */
+#define PM_SO_NO_FIXUP 128     /* do not issue the follow-up launch of the adaptive GM mesh: members
+                                  whose mesh outgrew the register solver stay flagged in `status`
+                                  (bit 3) with the 256-node solution                            */
 
 #define PM_SO_OP_EKMAN 1
 #define PM_SO_OP_GM 2

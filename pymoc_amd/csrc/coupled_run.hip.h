@@ -21,6 +21,7 @@
 #pragma once
 #include "thermwind.hip.h"
 #include "psi_so.hip.h"
+#include "launch.hip.h"
 
 namespace pm {
 
@@ -338,24 +339,11 @@ static int launch_so_tw_impl(const pm_psi_so &so, const pm_thermwind &tw, int tw
   const int s = so_lds_doubles(so.nz, so.ny, false, false);
   per = ((s > per ? s : per) + 1) & ~1;
   const size_t per_wave = (size_t)per * sizeof(double);
-  int wpb = 1, best = 0;  // as launch_thermwind_impl: the block size that keeps most waves on a CU
-  for (int w = TW_WAVES_PER_BLOCK; w >= 1; w >>= 1) {
-    int resident = (int)((160 * 1024) / (per_wave * w)) * w;
-    resident = resident > 16 ? 16 : resident;
-    if (resident > best) {
-      best = resident;
-      wpb = w;
-    }
-  }
+  const int wpb = waves_per_block(per_wave, TW_WAVES_PER_BLOCK, 16);  // (the thermal wind's registers)
   const size_t lds = per_wave * wpb;
-  if (lds > 160 * 1024) return fail(PM_EINVAL, "pm_so_tw_update needs %zu B of LDS per member", lds);
-  if (lds > 64 * 1024)
-    PM_HIP(hipFuncSetAttribute((const void *)k_so_tw_update<P, BIG>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > LDS_PER_CU) return fail(PM_EINVAL, "pm_so_tw_update needs %zu B of LDS per member", lds);
   const unsigned grid = (unsigned)((tw.n + wpb - 1) / wpb);
-  hipLaunchKernelGGL((k_so_tw_update<P, BIG>), dim3(grid), dim3(64 * wpb), lds, st, so, tw, tw_ops, per);
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return launch_dyn(k_so_tw_update<P, BIG>, grid, 64 * wpb, lds, st, so, tw, tw_ops, per);
 }
 
 // (the lane shapes the stand-alone kernels use for this nz: results are bit-identical to them)
@@ -368,34 +356,23 @@ int launch_so_tw_update(const pm_psi_so &so, const pm_thermwind &tw, int tw_ops,
                                  : launch_so_tw_impl<3, 1>(so, tw, tw_ops, st);
     case 4: return launch_so_tw_impl<4, 1>(so, tw, tw_ops, st);
   }
-  return -1;  // not covered: the caller issues the two launches
+  // (the caller issues the two launches)
+  return fail(PM_EINVAL, "pm_so_tw_update: shape not covered (nz=%d)", nz);
 }
 
 // ------------------------------------------------------------------------ launchers
 size_t run_lds_bytes(int kind, int nz, int nb, int ny);
-inline bool run_rows_aligned(const pm_columns &c, const double *wA, int P) {
-  auto al = [](const void *q) { return (((unsigned long long)q) & 15ull) == 0ull; };
-  return c.nz % P == 0 && al(c.b) && al(c.area) && al(c.kappa) && al(c.dAkappa) && al(wA);
-}
 
 template <int P, int BIG>
 static int launch_twocol_run_impl(const pm_twocol_loop &r, hipStream_t st) {
   const int wstride = run_wave_stride<P>(r.cols.nz, r.tw.nb, 0, false);
   const size_t lds = (size_t)(JfLds<P>::WAVE0 + JF_WAVES * wstride) * sizeof(double);
-  if (lds > 160 * 1024)
+  if (lds > LDS_PER_CU)
     return fail(PM_EINVAL, "pm_twocol_run: %zu B of LDS per block (nz=%d, nb=%d) exceed 160 KB",
                 lds, r.cols.nz, r.tw.nb);
   const unsigned grid = (unsigned)((r.tw.n + JF_WAVES - 1) / JF_WAVES);
-  const bool vec = run_rows_aligned(r.cols, r.wA, P);
-  auto go = [&](auto kernel) -> int {
-    if (lds > 64 * 1024)
-      PM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * JF_WAVES), lds, st, r, wstride);
-    PM_HIP(hipGetLastError());
-    return PM_OK;
-  };
-  return vec ? go(k_twocol_run<P, true, BIG>) : go(k_twocol_run<P, false, BIG>);
+  const auto kernel = rows_aligned(r.cols, r.wA, P) ? k_twocol_run<P, true, BIG> : k_twocol_run<P, false, BIG>;
+  return launch_dyn(kernel, grid, 64 * JF_WAVES, lds, st, r, wstride);
 }
 
 int launch_twocol_run(const pm_twocol_loop &r, hipStream_t st) {
@@ -412,37 +389,23 @@ static int launch_jn2018_run_impl(const pm_jn2018_loop &r, hipStream_t st) {
   const pm_jn2018 &a = r.jn;
   const int wstride = run_wave_stride<P>(a.cols.nz, r.tw.nb, a.ml.ny, true);
   const size_t lds = (size_t)(JfLds<P>::WAVE0 + JF_WAVES * wstride) * sizeof(double);
-  if (lds > 160 * 1024)
+  if (lds > LDS_PER_CU)
     return fail(PM_EINVAL, "pm_jn2018_run: %zu B of LDS per block (nz=%d, nb=%d) exceed 160 KB",
                 lds, a.cols.nz, r.tw.nb);
   const unsigned grid = (unsigned)((a.n + JF_WAVES - 1) / JF_WAVES);
-  auto al = [](const void *q) { return (((unsigned long long)q) & 15ull) == 0ull; };
-  const bool vec = run_rows_aligned(a.cols, a.wA, P) && al(a.Psi_SO);
+  const bool vec = rows_aligned(a.cols, a.wA, P) && aligned16(a.Psi_SO);
   const bool ct = (a.hints & PM_JN_CONTRACTED) != 0;
-  auto go = [&](auto kernel) -> int {
-    if (lds > 64 * 1024)
-      PM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * JF_WAVES), lds, st, a, r.tw, r.so, r.dt,
-                       r.sched, wstride);
-    PM_HIP(hipGetLastError());
-    return PM_OK;
-  };
-  if (ct && vec) return go(k_jn2018_run<P, true, true, BIG>);
-  if (ct) return go(k_jn2018_run<P, true, false, BIG>);
-  const int rc = vec ? go(k_jn2018_run<P, false, true, BIG>) : go(k_jn2018_run<P, false, false, BIG>);
-  if (rc != PM_OK) return rc;
+  const int rc = with_bools(
+      [&](auto ct_, auto vec_) {
+        return launch_dyn(k_jn2018_run<P, decltype(ct_)::value, decltype(vec_)::value, BIG>, grid,
+                          64 * JF_WAVES, lds, st, a, r.tw, r.so, r.dt, r.sched, wstride);
+      },
+      ct, vec);
+  if (rc != PM_OK || ct) return rc;
   // the IEEE leg of the members that left the launch (operands outside the division window)
   const size_t lds1 = (size_t)(JfLds<P>::WAVE0 + wstride) * sizeof(double);
-  const unsigned g1 = (unsigned)((a.n + 63) / 64 < 64 ? (a.n + 63) / 64 : 64);
-  if (vec)
-    hipLaunchKernelGGL((k_jn2018_run_ieee<P, true, BIG>), dim3(g1), dim3(64), lds1, st, a, r.tw,
-                       r.so, r.dt, r.sched, wstride);
-  else
-    hipLaunchKernelGGL((k_jn2018_run_ieee<P, false, BIG>), dim3(g1), dim3(64), lds1, st, a, r.tw,
-                       r.so, r.dt, r.sched, wstride);
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return launch_ieee_leg(k_jn2018_run_ieee<P, true, BIG>, k_jn2018_run_ieee<P, false, BIG>, vec, a.n,
+                         lds1, st, a, r.tw, r.so, r.dt, r.sched, wstride);
 }
 
 int launch_jn2018_run(const pm_jn2018_loop &r, hipStream_t st) {

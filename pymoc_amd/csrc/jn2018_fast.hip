@@ -1820,81 +1820,55 @@ void k_jn2018_split(pm_jn2018 a, double dt, int nsteps) {
 }
 
 template <int P>
-static void launch_split_kernel(const pm_jn2018 &a, double dt, int nsteps, bool vec, hipStream_t st) {
+static int launch_split_kernel(const pm_jn2018 &a, double dt, int nsteps, hipStream_t st) {
   const size_t lds = (size_t)JsLds<P>::TOTAL * sizeof(double);
   const unsigned grid = (unsigned)((a.n + JF_WAVES - 1) / JF_WAVES);
-  const bool ct = (a.hints & PM_JN_CONTRACTED) != 0;
-#define JS_LAUNCH(CT_, VEC_)                                                                     \
-  hipLaunchKernelGGL((k_jn2018_split<P, CT_, VEC_>), dim3(grid), dim3(64 * JF_WAVES), lds, st, a, \
-                     dt, nsteps)
-  if (ct && vec)
-    JS_LAUNCH(true, true);
-  else if (ct)
-    JS_LAUNCH(true, false);
-  else if (vec)
-    JS_LAUNCH(false, true);
-  else
-    JS_LAUNCH(false, false);
-#undef JS_LAUNCH
+  // 16-byte row accesses: every row starts 16-byte aligned and holds an even number of levels
+  const bool vec = rows_aligned(a.cols, a.wA, 2) && aligned16(a.Psi_SO);
+  return with_bools(
+      [&](auto ct, auto vec_) {
+        return launch_dyn(k_jn2018_split<P, decltype(ct)::value, decltype(vec_)::value>, grid,
+                          64 * JF_WAVES, lds, st, a, dt, nsteps);
+      },
+      (a.hints & PM_JN_CONTRACTED) != 0, vec);
 }
 
 template <int P>
 static int launch_fast(const pm_jn2018 &a, double dt, int nsteps, hipStream_t st) {
   const size_t lds = (size_t)JfLds<P>::TOTAL * sizeof(double);
   const unsigned grid = (unsigned)((a.n + JF_WAVES - 1) / JF_WAVES);
-  // 16-byte row accesses (jf_load_row): every row starts 16-byte aligned and holds whole lanes
-  auto al = [](const void *q) { return (((unsigned long long)q) & 15ull) == 0ull; };
-  const bool vec = a.cols.nz % P == 0 && al(a.cols.b) && al(a.cols.area) && al(a.cols.kappa) &&
-                   al(a.cols.dAkappa) && al(a.wA) && al(a.Psi_SO);
+  // 16-byte row accesses (jf_load_row)
+  const bool vec = rows_aligned(a.cols, a.wA, P) && aligned16(a.Psi_SO);
   const bool ct = (a.hints & PM_JN_CONTRACTED) != 0;
+  // PM_JN_DIV3_PROVEN: the caller's proof for every static denominator (pm_div3_proven)
+  const bool d3 = (a.hints & PM_JN_DIV3_PROVEN) != 0 && !ct;
   // round 5: both columns of a member side by side in the wave's two halves (k_jn2018_split).
   // Opt-in (PM_JN_SPLIT_LANES): 7 % fewer vector instructions per launch, measured a tie on
   // config 5; shapes 65..128 and 193..224
   const int PS = (a.cols.nz + 31) / 32;
-  const bool split = (a.hints & PM_JN_SPLIT_LANES) && (PS == 3 || PS == 4 || PS == 7);
-  if (split) {
-    // 16-byte row accesses: every row starts 16-byte aligned and holds an even number of levels
-    const bool v2 = a.cols.nz % 2 == 0 && al(a.cols.b) && al(a.cols.area) && al(a.cols.kappa) &&
-                    al(a.cols.dAkappa) && al(a.wA) && al(a.Psi_SO);
-    switch (PS) {
-      case 3: launch_split_kernel<3>(a, dt, nsteps, v2, st); break;
-      case 4: launch_split_kernel<4>(a, dt, nsteps, v2, st); break;
-      default: launch_split_kernel<7>(a, dt, nsteps, v2, st); break;
-    }
+  int rc;
+  if ((a.hints & PM_JN_SPLIT_LANES) && (PS == 3 || PS == 4 || PS == 7)) {
+    rc = PS == 3   ? launch_split_kernel<3>(a, dt, nsteps, st)
+         : PS == 4 ? launch_split_kernel<4>(a, dt, nsteps, st)
+                   : launch_split_kernel<7>(a, dt, nsteps, st);
+  } else {
+    rc = with_bools(
+        [&](auto ct_, auto vec_, auto d3_) {
+          constexpr bool CT = decltype(ct_)::value, D3 = decltype(d3_)::value;
+          if constexpr (CT && D3) {
+            return (int)PM_OK;  // (d3 implies !ct: no such kernel)
+          } else {
+            return launch_dyn(k_jn2018_fast<P, CT, decltype(vec_)::value, D3>, grid, 64 * JF_WAVES,
+                              lds, st, a, dt, nsteps);
+          }
+        },
+        ct, vec, d3);
   }
-#define JF_LAUNCH(CT_, VEC_)                                                                  \
-  hipLaunchKernelGGL((k_jn2018_fast<P, CT_, VEC_>), dim3(grid), dim3(64 * JF_WAVES), lds, st, a, \
-                     dt, nsteps)
-  // PM_JN_DIV3_PROVEN: the caller's proof for every static denominator (pm_div3_proven)
-  const bool d3 = (a.hints & PM_JN_DIV3_PROVEN) != 0 && !ct;
-  if (split)
-    ;
-  else if (d3 && vec)
-    hipLaunchKernelGGL((k_jn2018_fast<P, false, true, true>), dim3(grid), dim3(64 * JF_WAVES), lds, st,
-                       a, dt, nsteps);
-  else if (d3)
-    hipLaunchKernelGGL((k_jn2018_fast<P, false, false, true>), dim3(grid), dim3(64 * JF_WAVES), lds, st,
-                       a, dt, nsteps);
-  else if (ct && vec)
-    JF_LAUNCH(true, true);
-  else if (ct)
-    JF_LAUNCH(true, false);
-  else if (vec)
-    JF_LAUNCH(false, true);
-  else
-    JF_LAUNCH(false, false);
-#undef JF_LAUNCH
-  PM_HIP(hipGetLastError());
-  if (!ct && a.ml.status) {  // the IEEE leg of the members this launch flagged
-    const size_t lds1 = (size_t)(JfLds<P>::WAVE0 + JfLds<P>::PER_WAVE) * sizeof(double);
-    const unsigned g1 = (unsigned)((a.n + 63) / 64 < 64 ? (a.n + 63) / 64 : 64);
-    if (vec)
-      hipLaunchKernelGGL((k_jn2018_ieee<P, true>), dim3(g1), dim3(64), lds1, st, a, dt, nsteps);
-    else
-      hipLaunchKernelGGL((k_jn2018_ieee<P, false>), dim3(g1), dim3(64), lds1, st, a, dt, nsteps);
-    PM_HIP(hipGetLastError());
-  }
-  return PM_OK;
+  if (rc != PM_OK || ct || !a.ml.status) return rc;
+  // the IEEE leg of the members this launch flagged
+  const size_t lds1 = (size_t)(JfLds<P>::WAVE0 + JfLds<P>::PER_WAVE) * sizeof(double);
+  return launch_ieee_leg(k_jn2018_ieee<P, true>, k_jn2018_ieee<P, false>, vec, a.n, lds1, st, a, dt,
+                         nsteps);
 }
 
 bool jn2018_fast_applies(const pm_jn2018 &a) {

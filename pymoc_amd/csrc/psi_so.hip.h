@@ -25,6 +25,7 @@
 //    elements (in-lane merges + 6 DPP scan steps each) give every node its closing row.
 #pragma once
 #include "common.hip.h"
+#include "launch.hip.h"
 
 namespace pm {
 
@@ -1267,35 +1268,17 @@ template <int P, bool BVP>
 int launch_psi_so_impl(const pm_psi_so &a, int ops, hipStream_t st) {
   const bool adaptive = BVP && a.bvp_refine <= 0;
   const size_t per_wave = (size_t)so_lds_doubles(a.nz, a.ny, BVP, adaptive) * sizeof(double);
-  // waves per block: as many of SO_WAVES_PER_BLOCK, .../2, 1 as keeps the most waves on a CU
-  int wpb = 1, best = 0;
-  for (int w = SO_WAVES_PER_BLOCK; w >= 1; w >>= 1) {
-    int resident = (int)((160 * 1024) / (per_wave * w)) * w;
-    resident = resident > 32 ? 32 : resident;
-    if (resident > best) {
-      best = resident;
-      wpb = w;
-    }
-  }
+  const int wpb = waves_per_block(per_wave, SO_WAVES_PER_BLOCK, 32);
   const size_t lds = per_wave * wpb;
-  if (lds > 160 * 1024) return fail(PM_EINVAL, "psi_so needs %zu B of LDS per member", lds);
-  if (lds > 64 * 1024)
-    PM_HIP(hipFuncSetAttribute((const void *)k_psi_so<P, BVP>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > LDS_PER_CU) return fail(PM_EINVAL, "psi_so needs %zu B of LDS per member", lds);
   const unsigned grid = (unsigned)((a.n + wpb - 1) / wpb);
-  hipLaunchKernelGGL((k_psi_so<P, BVP>), dim3(grid), dim3(64 * wpb), lds, st, a, ops);
-  PM_HIP(hipGetLastError());
+  if (const int rc = launch_dyn(k_psi_so<P, BVP>, grid, 64 * wpb, lds, st, a, ops)) return rc;
   if constexpr (BVP && P <= SO_REG_NZ / 64) {
-    // (PYMOC_SO_NO_FIXUP=1 skips it: tests use that to see the flag the first launch leaves)
-    if (adaptive && a.status && (ops & PM_SO_OP_GM) && !getenv("PYMOC_SO_NO_FIXUP")) {
+    if (adaptive && a.status && (ops & PM_SO_OP_GM) && !(a.flags & PM_SO_NO_FIXUP)) {
       // members whose mesh outgrew the register-resident solver: redone by the general one
       const size_t lds_fix = (size_t)so_lds_doubles(a.nz, a.ny, true, true, true) * sizeof(double);
-      if (lds_fix > 64 * 1024)
-        PM_HIP(hipFuncSetAttribute((const void *)k_psi_so<P, BVP, true>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fix));
       const unsigned gfix = (unsigned)(a.n < 256 ? a.n : 256);
-      hipLaunchKernelGGL((k_psi_so<P, BVP, true>), dim3(gfix), dim3(64), lds_fix, st, a, ops);
-      PM_HIP(hipGetLastError());
+      return launch_dyn(k_psi_so<P, BVP, true>, gfix, 64, lds_fix, st, a, ops);
     }
   }
   return PM_OK;

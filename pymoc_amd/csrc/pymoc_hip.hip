@@ -497,6 +497,11 @@ int pm_graph_destroy(pm_graph_t graph) {
 }
 
 // -------------------------------------------------------------------- Column
+// the rows every column step reads
+static bool columns_rows_given(const pm_columns &c) {
+  return c.z && c.b && c.kappa && c.area && c.dAkappa && c.bs && c.bbot && c.N2min;
+}
+
 static int column_shape(int nz, int lanes_per_col, int *G_out, int *P_out) {
   // lanes_per_col = 0: one wave per column, measured on MI355X (profiles/r01_sweep_columns.txt)
   // to win at every ensemble size from 1024 to 65536 columns at nz=100
@@ -531,8 +536,7 @@ static int column_call(const pm_columns *cols, const double *wA, const double *v
              "bad batch shape ncols=%d nz=%d (need nz in [2,1024])", c.ncols, c.nz);
   PM_REQUIRE(c.nsel >= 1 && c.nsel <= 2, "nsel must be 1 or 2 (got %d)", c.nsel);
   if (c.ncols == 0) return PM_OK;  // empty batch: nothing to do, pointers may be NULL
-  PM_REQUIRE(c.z && c.b && c.kappa && c.area && c.dAkappa && c.bs && c.bbot && c.N2min,
-             "pm_columns has a NULL required pointer");
+  PM_REQUIRE(columns_rows_given(c), "pm_columns has a NULL required pointer");
   PM_REQUIRE(nsteps >= 0, "nsteps < 0");
   PM_REQUIRE((ops & ~(PM_OP_TIMESTEP | PM_OP_WEFF | PM_OP_CONTRACTED | PM_OP_WA_PSI | PM_OP_WA_TWOBASIN)) == 0,
              "unknown op bits 0x%x", ops);
@@ -616,48 +620,90 @@ int pm_thermwind_residuals(int32_t m, const double *x, const double *y0, const d
   return PM_OK;
 }
 
+// ------------------------------------------------------- descriptor checks
+// One check per descriptor, shared by every entry point that takes it.  `who` names the entry
+// point and the argument; limits that differ between entry points are arguments.  `ptrs`: the
+// call has work for this batch, so its required arrays must be given (an entry point that
+// returns early for an empty batch passes false).
+static int check_thermwind(const char *who, const pm_thermwind &a, int ops, int nz_max, bool ptrs) {
+  PM_REQUIRE(a.n >= 0 && a.nz >= 2 && a.nz <= nz_max, "%s: bad shape n=%d nz=%d (nz in [2,%d])", who,
+             a.n, a.nz, nz_max);
+  PM_REQUIRE((ops & ~15) == 0 && ops != 0, "%s: bad ops 0x%x", who, ops);
+  PM_REQUIRE(!(ops & PM_TW_PSIBZ) || (ops & PM_TW_PSIB), "%s: ops 0x%x, PM_TW_PSIBZ needs PM_TW_PSIB", who, ops);
+  PM_REQUIRE(!(ops & PM_TW_PSIB) || a.nb >= 1, "%s: nb must be >= 1 (nb=%d)", who, a.nb);
+  if (!ptrs) return PM_OK;
+  PM_REQUIRE(a.z && a.b1 && a.b2 && a.Psi, "%s has a NULL required pointer", who);
+  PM_REQUIRE(!(ops & PM_TW_SOLVE) || a.f, "%s has a NULL f", who);
+  return PM_OK;
+}
+
+static int check_psi_so(const char *who, const pm_psi_so &a, int ops, int nz_max, bool ptrs) {
+  PM_REQUIRE(a.n >= 0 && a.nz >= 2 && a.nz <= nz_max && a.ny >= 2 && a.ny <= 2048,
+             "%s: bad shape n=%d nz=%d ny=%d (nz in [2,%d], ny in [2,2048])", who, a.n, a.nz, a.ny, nz_max);
+  PM_REQUIRE(ops >= 1 && ops <= 3, "%s: bad ops %d", who, ops);
+  if (!ptrs) return PM_OK;
+  PM_REQUIRE(a.z && a.y && a.b && a.bs && a.tau && a.KGM && a.Psi_Ek, "%s has a NULL required pointer", who);
+  PM_REQUIRE(!(ops & PM_SO_OP_GM) || (a.Psi && a.Psi_GM), "%s has a NULL Psi / Psi_GM", who);
+  return PM_OK;
+}
+
+// basin_rows: b_basin / Psi_b are read (pm_jn2018 takes them from its columns and Psi_SO)
+static int check_so_ml(const char *who, const char *part, const pm_so_ml &a, int nz_max,
+                       bool basin_rows, bool ptrs) {
+  PM_REQUIRE(a.n >= 0 && a.nz >= 2 && a.nz <= nz_max && a.ny >= 3 && a.ny <= 2048,
+             "%s%s: bad shape n=%d nz=%d ny=%d (nz in [2,%d], ny in [3,2048])", who, part, a.n, a.nz, a.ny, nz_max);
+  if (!ptrs) return PM_OK;
+  PM_REQUIRE(a.y && a.bs && a.surflux && a.rest_mask && a.b_rest && (!basin_rows || (a.b_basin && a.Psi_b)),
+             "%s%s has a NULL required pointer", who, part);
+  return PM_OK;
+}
+
+// with its cols and ml; the arrays are required of an empty batch too
+static int check_jn2018(const char *who, const pm_jn2018 &a) {
+  const pm_columns &c = a.cols;
+  PM_REQUIRE(a.n >= 0 && c.ncols == 2 * a.n && a.ml.n == a.n && a.ml.nz == c.nz,
+             "%s: inconsistent batch sizes n=%d ncols=%d ml.n=%d nz=%d ml.nz=%d", who, a.n, c.ncols, a.ml.n,
+             c.nz, a.ml.nz);
+  PM_REQUIRE(c.nz >= 2 && c.nz <= 256, "%s: bad shape nz=%d (the fused loop needs nz in [2,256])", who, c.nz);
+  if (const int rc = check_so_ml(who, ".ml", a.ml, 256, false, true)) return rc;
+  PM_REQUIRE(c.nsel == 2 && c.ksel && columns_rows_given(c), "%s.cols has a NULL pointer or nsel != 2 (nsel=%d)",
+             who, c.nsel);
+  PM_REQUIRE(a.wA && a.Psi_SO && a.Psi_res_b && a.Psi_res_n, "%s has a NULL pointer", who);
+  return PM_OK;
+}
+
+constexpr int TW_RUN_OPS = PM_TW_SOLVE | PM_TW_PSIB | PM_TW_PSIBZ;  // a run kernel's thermal-wind phase
+static int check_schedule(const char *who, const pm_run_schedule &s) {
+  PM_REQUIRE(s.n_first >= 0 && s.n_updates >= 0 && s.m_steps >= 0 && s.n_last >= 0,
+             "%s: bad schedule %d, %d x %d, %d", who, s.n_first, s.n_updates, s.m_steps, s.n_last);
+  return PM_OK;
+}
+
 // ------------------------------------------------------------- Psi_Thermwind
 int pm_thermwind_update(const pm_thermwind *tw, int32_t ops, pm_stream_t stream) {
   PM_REQUIRE(tw, "tw is NULL");
-  const pm_thermwind &a = *tw;
-  PM_REQUIRE(a.n >= 0 && a.nz >= 2 && a.nz <= 1024, "bad shape n=%d nz=%d", a.n, a.nz);
-  PM_REQUIRE((ops & ~15) == 0 && ops != 0, "bad ops 0x%x", ops);
-  PM_REQUIRE(!(ops & PM_TW_PSIBZ) || (ops & PM_TW_PSIB), "PM_TW_PSIBZ needs PM_TW_PSIB");
-  PM_REQUIRE(!(ops & PM_TW_PSIB) || a.nb >= 1, "nb must be >= 1");
-  if (a.n == 0) return PM_OK;
-  PM_REQUIRE(a.z && a.b1 && a.b2 && a.Psi, "pm_thermwind has a NULL required pointer");
-  PM_REQUIRE(!(ops & PM_TW_SOLVE) || a.f, "f is NULL");
-  if (a.n == 0) return PM_OK;
-  return dispatch_thermwind(a, ops, resolve_stream(stream));
+  if (const int rc = check_thermwind("pm_thermwind_update: pm_thermwind", *tw, ops, 1024, tw->n != 0)) return rc;
+  if (tw->n == 0) return PM_OK;
+  return dispatch_thermwind(*tw, ops, resolve_stream(stream));
 }
 
 // -------------------------------------------------------------------- Psi_SO
 int pm_psi_so_update(const pm_psi_so *so, int32_t ops, pm_stream_t stream) {
   PM_REQUIRE(so, "so is NULL");
   const pm_psi_so &a = *so;
-  PM_REQUIRE(a.n >= 0 && a.nz >= 2 && a.nz <= 512 && a.ny >= 2 && a.ny <= 2048,
-             "bad shape n=%d nz=%d ny=%d", a.n, a.nz, a.ny);
-  PM_REQUIRE(ops >= 1 && ops <= 3, "bad ops %d", ops);
+  if (const int rc = check_psi_so("pm_psi_so_update: pm_psi_so", a, ops, 512, a.n != 0)) return rc;
   if (a.n == 0) return PM_OK;
-  PM_REQUIRE(a.z && a.y && a.b && a.bs && a.tau && a.KGM && a.Psi_Ek,
-             "pm_psi_so has a NULL required pointer");
-  PM_REQUIRE(!(ops & PM_SO_OP_GM) || (a.Psi && a.Psi_GM), "Psi / Psi_GM is NULL");
-  PM_REQUIRE(a.bvp_refine >= -1 && a.bvp_refine <= 256, "bad bvp_refine (<= 0: adaptive mesh, R > 0: fixed R-fold mesh)");
-  if (a.n == 0) return PM_OK;
+  PM_REQUIRE(a.bvp_refine >= -1 && a.bvp_refine <= 256,
+             "pm_psi_so_update: bad bvp_refine %d (<= 0: adaptive mesh, R > 0: fixed R-fold mesh)", a.bvp_refine);
   return dispatch_psi_so(a, ops, resolve_stream(stream));
 }
 
 // --------------------------------------------------------------------- SO_ML
 int pm_so_ml_step(const pm_so_ml *ml, double dt, pm_stream_t stream) {
   PM_REQUIRE(ml, "ml is NULL");
-  const pm_so_ml &a = *ml;
-  PM_REQUIRE(a.n >= 0 && a.nz >= 2 && a.ny >= 3 && a.nz <= 4096 && a.ny <= 2048,
-             "bad shape n=%d nz=%d ny=%d", a.n, a.nz, a.ny);
-  if (a.n == 0) return PM_OK;
-  PM_REQUIRE(a.y && a.bs && a.b_basin && a.Psi_b && a.surflux && a.rest_mask && a.b_rest,
-             "pm_so_ml has a NULL required pointer");
-  if (a.n == 0) return PM_OK;
-  return launch_so_ml(a, dt, resolve_stream(stream));
+  if (const int rc = check_so_ml("pm_so_ml_step: pm_so_ml", "", *ml, 4096, true, ml->n != 0)) return rc;
+  if (ml->n == 0) return PM_OK;
+  return launch_so_ml(*ml, dt, resolve_stream(stream));
 }
 
 int pm_jn2018_bc_switch(const pm_jn2018_bc *bc, pm_stream_t stream) {
@@ -677,22 +723,12 @@ int pm_jn2018_bc_switch(const pm_jn2018_bc *bc, pm_stream_t stream) {
 int pm_jn2018_steps(const pm_jn2018 *jn, double dt, int32_t nsteps, pm_stream_t stream) {
   PM_REQUIRE(jn, "jn is NULL");
   const pm_jn2018 &a = *jn;
-  const pm_columns &c = a.cols;
-  PM_REQUIRE(a.n >= 0 && c.ncols == 2 * a.n && a.ml.n == a.n && a.ml.nz == c.nz,
-             "inconsistent batch sizes n=%d ncols=%d ml.n=%d", a.n, c.ncols, a.ml.n);
-  PM_REQUIRE(c.nz >= 2 && c.nz <= 256 && a.ml.ny >= 3 && a.ml.ny <= 2048,
-             "bad shape nz=%d ny=%d (fused loop needs nz <= 256)", c.nz, a.ml.ny);
-  PM_REQUIRE(c.nsel == 2 && c.ksel && c.z && c.b && c.kappa && c.area && c.dAkappa && c.bs &&
-                 c.bbot && c.N2min,
-             "pm_jn2018.cols has a NULL pointer or nsel != 2");
-  PM_REQUIRE(a.wA && a.Psi_SO && a.Psi_res_b && a.Psi_res_n, "pm_jn2018 has a NULL pointer");
-  PM_REQUIRE(a.ml.y && a.ml.bs && a.ml.surflux && a.ml.rest_mask && a.ml.b_rest,
-             "pm_jn2018.ml has a NULL pointer");
-  PM_REQUIRE(nsteps >= 0, "nsteps < 0");
+  if (const int rc = check_jn2018("pm_jn2018_steps: jn", a)) return rc;
+  PM_REQUIRE(nsteps >= 0, "pm_jn2018_steps: nsteps %d < 0", nsteps);
   if (a.n == 0 || nsteps == 0) return PM_OK;
   hipStream_t st = resolve_stream(stream);
   if (jn2018_fast_applies(a)) return launch_jn2018_fast(a, dt, nsteps, st);
-  switch ((c.nz + 63) / 64) {
+  switch ((a.cols.nz + 63) / 64) {
     case 1: return launch_jn2018_steps<1>(a, dt, nsteps, st);
     case 2: return launch_jn2018_steps<2>(a, dt, nsteps, st);
     case 3: return launch_jn2018_steps<3>(a, dt, nsteps, st);
@@ -702,23 +738,17 @@ int pm_jn2018_steps(const pm_jn2018 *jn, double dt, int32_t nsteps, pm_stream_t 
 
 int pm_so_tw_update(const pm_psi_so *so, const pm_thermwind *tw, int32_t tw_ops,
                     pm_stream_t stream) {
-  PM_REQUIRE(so && tw, "NULL argument");
+  PM_REQUIRE(so && tw, "pm_so_tw_update: NULL argument");
   const pm_psi_so &a = *so;
   const pm_thermwind &t = *tw;
-  PM_REQUIRE(a.n == t.n && a.nz == t.nz && a.n >= 0, "inconsistent sizes");
-  PM_REQUIRE(t.nz >= 2 && t.nz <= 256 && a.ny >= 2 && a.ny <= 2048 && t.nb >= 1,
-             "pm_so_tw_update: nz <= 256 (nz=%d)", t.nz);
+  PM_REQUIRE(a.n == t.n && a.nz == t.nz && a.n >= 0,
+             "pm_so_tw_update: inconsistent sizes n=%d / %d, nz=%d / %d", a.n, t.n, a.nz, t.nz);
+  if (const int rc = check_psi_so("pm_so_tw_update: pm_psi_so", a, PM_SO_OP_SOLVE, 256, a.n != 0)) return rc;
+  if (const int rc = check_thermwind("pm_so_tw_update: pm_thermwind", t, tw_ops, 256, a.n != 0)) return rc;
+  PM_REQUIRE(t.nb >= 1, "pm_so_tw_update: nb must be >= 1 (nb=%d)", t.nb);
   PM_REQUIRE(!(a.flags & PM_SO_HAS_C), "pm_so_tw_update: Psi_SO without the boundary-value smoother");
-  PM_REQUIRE((tw_ops & ~15) == 0 && tw_ops != 0 && (!(tw_ops & PM_TW_PSIBZ) || (tw_ops & PM_TW_PSIB)),
-             "bad thermal-wind ops 0x%x", tw_ops);
   if (a.n == 0) return PM_OK;
-  PM_REQUIRE(a.z && a.y && a.b && a.bs && a.tau && a.KGM && a.Psi && a.Psi_Ek && a.Psi_GM,
-             "pm_psi_so has a NULL required pointer");
-  PM_REQUIRE(t.z && t.b1 && t.b2 && t.Psi && (!(tw_ops & PM_TW_SOLVE) || t.f),
-             "pm_thermwind has a NULL required pointer");
-  const int rc = launch_so_tw_update(a, t, tw_ops, resolve_stream(stream));
-  if (rc == -1) return fail(PM_EINVAL, "pm_so_tw_update: shape not covered (nz=%d)", t.nz);
-  return rc;
+  return launch_so_tw_update(a, t, tw_ops, resolve_stream(stream));
 }
 
 int pm_run_lds_bytes(int32_t kind, int32_t nz, int32_t nb, int32_t ny, size_t *bytes) {
@@ -732,17 +762,19 @@ int pm_twocol_run(const pm_twocol_loop *run, pm_stream_t stream) {
   const pm_twocol_loop &r = *run;
   const pm_columns &c = r.cols;
   const pm_thermwind &t = r.tw;
-  PM_REQUIRE(t.n >= 0 && c.ncols == 2 * t.n && t.nz == c.nz, "inconsistent sizes n=%d ncols=%d",
-             t.n, c.ncols);
-  PM_REQUIRE(c.nz >= 4 && c.nz <= 256 && t.nb >= 1, "pm_twocol_run needs 4 <= nz <= 256 (nz=%d)", c.nz);
-  PM_REQUIRE(c.nsel >= 1 && c.nsel <= 2 && (c.nsel == 1 || c.ksel), "bad nsel / ksel");
   const pm_run_schedule &s = r.sched;
-  PM_REQUIRE(s.n_first >= 0 && s.n_updates >= 0 && s.m_steps >= 0 && s.n_last >= 0, "bad schedule");
-  if (t.n == 0 || (s.n_first == 0 && s.n_updates == 0)) return PM_OK;
-  PM_REQUIRE(c.z && c.b && c.kappa && c.area && c.dAkappa && c.bs && c.bbot && c.N2min && c.flags,
-             "pm_twocol_loop.cols has a NULL required pointer");
-  PM_REQUIRE(t.z && t.b1 && t.b2 && t.f && t.Psi && t.wA1 && t.wA2 && r.wA,
-             "pm_twocol_loop.tw has a NULL required pointer");
+  PM_REQUIRE(t.n >= 0 && c.ncols == 2 * t.n && t.nz == c.nz,
+             "pm_twocol_run: inconsistent sizes n=%d ncols=%d, nz=%d / %d", t.n, c.ncols, t.nz, c.nz);
+  const bool work = t.n != 0 && (s.n_first != 0 || s.n_updates != 0);
+  if (const int rc = check_thermwind("pm_twocol_run: tw", t, TW_RUN_OPS, 256, work)) return rc;
+  PM_REQUIRE(c.nz >= 4, "pm_twocol_run needs 4 <= nz <= 256 (nz=%d)", c.nz);
+  PM_REQUIRE(c.nsel >= 1 && c.nsel <= 2 && (c.nsel == 1 || c.ksel),
+             "pm_twocol_run: bad nsel / ksel (nsel=%d)", c.nsel);
+  if (const int rc = check_schedule("pm_twocol_run", s)) return rc;
+  if (!work) return PM_OK;
+  PM_REQUIRE(columns_rows_given(c) && c.flags, "pm_twocol_run: cols has a NULL required pointer");
+  PM_REQUIRE(t.wA1 && t.wA2 && r.wA,
+             "pm_twocol_run: tw has a NULL required pointer (wA1, wA2 and the loop's wA)");
   PM_REQUIRE(!t.b1_mid && !t.b2_mid && !t.Psi_SO, "pm_twocol_run: array profiles, no SO channel");
   return launch_twocol_run(r, resolve_stream(stream));
 }
@@ -751,26 +783,19 @@ int pm_jn2018_run(const pm_jn2018_loop *run, pm_stream_t stream) {
   PM_REQUIRE(run, "run is NULL");
   const pm_jn2018_loop &r = *run;
   const pm_jn2018 &a = r.jn;
-  const pm_columns &c = a.cols;
-  PM_REQUIRE(a.n >= 0 && c.ncols == 2 * a.n && a.ml.n == a.n && a.ml.nz == c.nz && r.tw.n == a.n &&
-                 r.tw.nz == c.nz && r.so.n == a.n && r.so.nz == c.nz && r.so.ny == a.ml.ny,
-             "inconsistent batch sizes n=%d", a.n);
+  if (const int rc = check_jn2018("pm_jn2018_run: jn", a)) return rc;
+  PM_REQUIRE(r.tw.n == a.n && r.tw.nz == a.cols.nz && r.so.n == a.n && r.so.nz == a.cols.nz &&
+                 r.so.ny == a.ml.ny,
+             "pm_jn2018_run: inconsistent batch sizes n=%d / %d / %d, nz=%d / %d / %d, ny=%d / %d", a.n,
+             r.tw.n, r.so.n, a.cols.nz, r.tw.nz, r.so.nz, a.ml.ny, r.so.ny);
   PM_REQUIRE(jn2018_fast_applies(a), "pm_jn2018_run needs PM_JN_UNIFORM_AREA, ny <= 64, 4 <= nz <= 256, ml.status");
-  PM_REQUIRE(c.nsel == 2 && c.ksel && c.z && c.b && c.kappa && c.area && c.dAkappa && c.bs &&
-                 c.bbot && c.N2min,
-             "pm_jn2018_loop.jn.cols has a NULL pointer or nsel != 2");
-  PM_REQUIRE(a.wA && a.Psi_SO && a.Psi_res_b && a.Psi_res_n, "pm_jn2018_loop.jn has a NULL pointer");
-  PM_REQUIRE(a.ml.y && a.ml.bs && a.ml.surflux && a.ml.rest_mask && a.ml.b_rest && a.ml.ny >= 3,
-             "pm_jn2018_loop.jn.ml has a NULL pointer");
-  PM_REQUIRE(r.tw.z && r.tw.b1 && r.tw.b2 && r.tw.f && r.tw.Psi && r.tw.nb >= 1 && !r.tw.b1_mid &&
-                 !r.tw.b2_mid,
-             "pm_jn2018_loop.tw has a NULL required pointer");
-  PM_REQUIRE(r.so.z && r.so.y && r.so.b && r.so.bs && r.so.tau && r.so.KGM && r.so.Psi &&
-                 r.so.Psi_Ek && r.so.Psi_GM && !(r.so.flags & PM_SO_HAS_C),
-             "pm_jn2018_loop.so has a NULL required pointer (or the boundary-value smoother)");
-  const pm_run_schedule &s = r.sched;
-  PM_REQUIRE(s.n_first >= 0 && s.n_updates >= 0 && s.m_steps >= 0 && s.n_last >= 0, "bad schedule");
-  if (a.n == 0 || (s.n_first == 0 && s.n_updates == 0)) return PM_OK;
+  // (an empty batch names its arrays too, as for pm_jn2018_steps)
+  if (const int rc = check_thermwind("pm_jn2018_run: tw", r.tw, TW_RUN_OPS, 256, true)) return rc;
+  PM_REQUIRE(!r.tw.b1_mid && !r.tw.b2_mid, "pm_jn2018_run: tw takes array profiles (no b1_mid / b2_mid)");
+  if (const int rc = check_psi_so("pm_jn2018_run: so", r.so, PM_SO_OP_SOLVE, 256, true)) return rc;
+  PM_REQUIRE(!(r.so.flags & PM_SO_HAS_C), "pm_jn2018_run: so without the boundary-value smoother");
+  if (const int rc = check_schedule("pm_jn2018_run", r.sched)) return rc;
+  if (a.n == 0 || (r.sched.n_first == 0 && r.sched.n_updates == 0)) return PM_OK;
   return launch_jn2018_run(r, resolve_stream(stream));
 }
 

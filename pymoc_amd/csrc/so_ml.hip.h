@@ -19,6 +19,7 @@
 #pragma once
 #include "column.hip.h"
 #include "common.hip.h"
+#include "launch.hip.h"
 
 namespace pm {
 
@@ -837,17 +838,11 @@ inline size_t ml_prop_bytes(int ny) {
 #ifndef PM_SO_ML_DEVICE_FUNCTIONS_ONLY
 inline int launch_so_ml(const pm_so_ml &a, double dt, hipStream_t st) {
   const size_t per_wave = ml_lds_bytes(a.nz, a.ny), prop = ml_prop_bytes(a.ny);
-  int wpb = ML_WAVES_PER_BLOCK;
-  while (wpb > 1 && per_wave * wpb + prop > 160 * 1024) wpb >>= 1;
+  const int wpb = waves_per_block_fitting(per_wave, prop, ML_WAVES_PER_BLOCK);
   const size_t lds = per_wave * wpb + prop;
-  if (lds > 160 * 1024) return fail(PM_EINVAL, "so_ml needs %zu B of LDS per member", lds);
-  if (lds > 64 * 1024)
-    PM_HIP(hipFuncSetAttribute((const void *)k_so_ml_step,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > LDS_PER_CU) return fail(PM_EINVAL, "so_ml needs %zu B of LDS per member", lds);
   const unsigned grid = (unsigned)((a.n + wpb - 1) / wpb);
-  hipLaunchKernelGGL(k_so_ml_step, dim3(grid), dim3(64 * wpb), lds, st, a, dt);
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return launch_dyn(k_so_ml_step, grid, 64 * wpb, lds, st, a, dt);
 }
 
 #endif
@@ -855,27 +850,16 @@ inline int launch_so_ml(const pm_so_ml &a, double dt, hipStream_t st) {
 template <int P>
 int launch_jn2018_steps(const pm_jn2018 &a, double dt, int nsteps, hipStream_t st) {
   const size_t per_wave = ml_lds_bytes(a.cols.nz, a.ml.ny), prop = ml_prop_bytes(a.ml.ny);
-  int wpb = ML_WAVES_PER_BLOCK;
-  while (wpb > 1 && per_wave * wpb + prop > 160 * 1024) wpb >>= 1;
+  const int wpb = waves_per_block_fitting(per_wave, prop, ML_WAVES_PER_BLOCK);
   const size_t lds = per_wave * wpb + prop;
-  if (lds > 160 * 1024) return fail(PM_EINVAL, "jn2018 needs %zu B of LDS per member", lds);
+  if (lds > LDS_PER_CU) return fail(PM_EINVAL, "jn2018 needs %zu B of LDS per member", lds);
   const unsigned grid = (unsigned)((a.n + wpb - 1) / wpb);
-  const bool ua = (a.hints & PM_JN_UNIFORM_AREA) != 0;
-  auto go = [&](auto kernel) -> int {
-    if (lds > 64 * 1024)
-      PM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * wpb), lds, st, a, dt, nsteps);
-    return PM_OK;
-  };
-  int rc;
-  if (a.ml.ny <= 64)
-    rc = ua ? go(k_jn2018_steps<P, true, true>) : go(k_jn2018_steps<P, true, false>);
-  else
-    rc = ua ? go(k_jn2018_steps<P, false, true>) : go(k_jn2018_steps<P, false, false>);
-  if (rc != PM_OK) return rc;
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return with_bools(
+      [&](auto pcr, auto ua) {
+        return launch_dyn(k_jn2018_steps<P, decltype(pcr)::value, decltype(ua)::value>, grid,
+                          64 * wpb, lds, st, a, dt, nsteps);
+      },
+      a.ml.ny <= 64, (a.hints & PM_JN_UNIFORM_AREA) != 0);
 }
 
 // the residency-first rebuild of the fused loop (jn2018_fast.hip): uniform Area, ny <= 64

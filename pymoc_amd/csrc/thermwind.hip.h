@@ -19,6 +19,7 @@
 #pragma once
 #include <type_traits>
 #include "common.hip.h"
+#include "launch.hip.h"
 
 namespace pm {
 
@@ -1263,26 +1264,12 @@ __global__ void k_thermwind_residuals(int m, const double *x, const double *y0, 
 template <int P, int BIG>
 int launch_thermwind_impl(const pm_thermwind &a, int ops, hipStream_t st) {
   const size_t per_wave = (size_t)tw_lds_doubles(a.nz, a.nb) * sizeof(double);
-  // waves per block: as many of TW_WAVES_PER_BLOCK, .../2, 1 as keeps the most waves on a CU
-  // (nz = 200: 14 KB per wave -- blocks of 4 would leave room for 8 waves, single waves for 11)
-  int wpb = 1, best = 0;
-  for (int w = TW_WAVES_PER_BLOCK; w >= 1; w >>= 1) {
-    int resident = (int)((160 * 1024) / (per_wave * w)) * w;
-    resident = resident > 16 ? 16 : resident;  // 4 waves per SIMD is all the registers allow
-    if (resident > best) {
-      best = resident;
-      wpb = w;
-    }
-  }
+  // (16 resident waves: 4 per SIMD is all the registers allow)
+  const int wpb = waves_per_block(per_wave, TW_WAVES_PER_BLOCK, 16);
   const size_t lds = per_wave * wpb;
-  if (lds > 160 * 1024) return fail(PM_EINVAL, "thermwind needs %zu B of LDS per member", lds);
-  if (lds > 64 * 1024)
-    PM_HIP(hipFuncSetAttribute((const void *)k_thermwind<P, BIG>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > LDS_PER_CU) return fail(PM_EINVAL, "thermwind needs %zu B of LDS per member", lds);
   const unsigned grid = (unsigned)((a.n + wpb - 1) / wpb);
-  hipLaunchKernelGGL((k_thermwind<P, BIG>), dim3(grid), dim3(64 * wpb), lds, st, a, ops);
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return launch_dyn(k_thermwind<P, BIG>, grid, 64 * wpb, lds, st, a, ops);
 }
 
 template <int P>

@@ -20,11 +20,13 @@ def _ptr(x):
 
 class PsiSOBatch(object):
   """n members on shared grids z, y.  `b` [n,nz] and `bs` [n,ny] are device arrays (or raw
-  device pointers into other batches' state) read at every update()."""
+  device pointers into other batches' state) read at every update().  fixup=False sets
+  PM_SO_NO_FIXUP: members whose adaptive GM mesh outgrew the register solver stay flagged in
+  `status` instead of being redone by the follow-up launch."""
 
   def __init__(self, z, y, n, tau, KGM=1e3, f=1.2e-4, rho=1030, L=1e7, c=None,
                bvp_with_Ek=False, Hsill=None, HEk=None, Htapertop=None, Htaperbot=None,
-               smax=0.01, bvp_refine=0, stream=None, z_dev=None, diagnostics=False):
+               smax=0.01, bvp_refine=0, stream=None, z_dev=None, diagnostics=False, fixup=True):
     _lib.require_device()
     self.z_host = np.ascontiguousarray(z, dtype=np.float64)
     self.y_host = np.ascontiguousarray(y, dtype=np.float64)
@@ -40,6 +42,7 @@ class PsiSOBatch(object):
     self.opts = dict(f=f, rho=rho, L=L, c=c, bvp_with_Ek=bvp_with_Ek, Hsill=Hsill, HEk=HEk,
                      Htapertop=Htapertop, Htaperbot=Htaperbot, smax=smax)
     self.bvp_refine = int(bvp_refine)
+    self.fixup = bool(fixup)
     self.Psi = DeviceArray.zeros((self.n, self.nz), stream=stream)
     self.Psi_Ek = DeviceArray.zeros((self.n, self.nz), stream=stream)
     self.Psi_GM = DeviceArray.zeros((self.n, self.nz), stream=stream)
@@ -87,6 +90,8 @@ class PsiSOBatch(object):
       setattr(d, name, float(o[name]) if o[name] is not None else 0.0)
     if o["bvp_with_Ek"]:
       fl |= _lib.PM_SO_BVP_WITH_EK
+    if not self.fixup:
+      fl |= _lib.PM_SO_NO_FIXUP
     d.flags, d.bvp_refine, d.reserved = fl, self.bvp_refine, 0
     d.z, d.y, d.b, d.bs = self.z.ptr, self.y.ptr, _ptr(b), _ptr(bs)
     d.tau, d.KGM = self.tau.ptr, self.KGM.ptr

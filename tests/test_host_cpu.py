@@ -102,6 +102,299 @@ def test_cabi_rejects_bad_arguments_before_touching_the_device():
   assert L.pm_equi_column_scratch_doubles(64) >= 64 * 100
 
 
+def test_cabi_bad_argument_table_of_the_per_member_entries():
+  """Every per-member entry point against descriptors that are wrong in exactly one way (each
+  shape limit from both sides, each required pointer NULL, bad ops, sizes that disagree between
+  descriptors, a bad schedule, PM_SO_HAS_C where it is refused) and against batches with nothing
+  to do: the return code and a word of the message.  The stand-in pointers are never
+  dereferenced: a row is either refused or returns before any launch (an accepted shape limit is
+  shown on an empty batch)."""
+  from pymoc_amd import _lib
+  L, C = _lib.lib, ctypes
+  A = 0x10000
+  OK, EINVAL = _lib.PM_OK, _lib.PM_EINVAL
+
+  def fill(obj, names, **kw):
+    for f in names.split():
+      setattr(obj, f, A)
+    for k, v in kw.items():
+      setattr(obj, k, v)
+    return obj
+
+  def cols(ncols, nsel):
+    return fill(_lib.pm_columns(), "z b kappa area dAkappa bs bbot N2min flags ksel",
+                ncols=ncols, nz=100, nsel=nsel)
+
+  def tw():
+    return fill(_lib.pm_thermwind(), "z b1 b2 f Psi", n=2, nz=100, nb=50)
+
+  def so():
+    return fill(_lib.pm_psi_so(), "z y b bs tau KGM Psi Psi_Ek Psi_GM", n=2, nz=100, ny=40)
+
+  def ml():
+    return fill(_lib.pm_so_ml(), "y bs b_basin Psi_b surflux rest_mask b_rest status", n=2, nz=100,
+                ny=40)
+
+  def jn():
+    j = fill(_lib.pm_jn2018(), "wA Psi_SO Psi_res_b Psi_res_n", n=2, hints=_lib.PM_JN_UNIFORM_AREA)
+    j.cols, j.ml = cols(4, 2), ml()
+    return j
+
+  def sched():
+    return _lib.pm_run_schedule(1, 1, 1, 1)
+
+  def twocol():
+    r = fill(_lib.pm_twocol_loop(), "wA", dt=1.)
+    r.cols, r.tw, r.sched = cols(4, 1), fill(tw(), "wA1 wA2"), sched()
+    return r
+
+  def jnrun():
+    r = _lib.pm_jn2018_loop()
+    r.jn, r.tw, r.so, r.dt, r.sched = jn(), tw(), so(), 1., sched()
+    return r
+
+  # entry -> (the valid descriptors, the call); "@name" edits replace a call argument
+  entries = {
+      "tw": (lambda: dict(tw=tw()), dict(ops=7),
+             lambda d, a: L.pm_thermwind_update(C.byref(d["tw"]), a["ops"], None)),
+      "so": (lambda: dict(so=so()), dict(ops=3),
+             lambda d, a: L.pm_psi_so_update(C.byref(d["so"]), a["ops"], None)),
+      "ml": (lambda: dict(ml=ml()), dict(),
+             lambda d, a: L.pm_so_ml_step(C.byref(d["ml"]), 1., None)),
+      "so_tw": (lambda: dict(so=so(), tw=tw()), dict(ops=7),
+                lambda d, a: L.pm_so_tw_update(C.byref(d["so"]), C.byref(d["tw"]), a["ops"], None)),
+      "steps": (lambda: dict(jn=jn()), dict(nsteps=5),
+                lambda d, a: L.pm_jn2018_steps(C.byref(d["jn"]), 1., a["nsteps"], None)),
+      "run": (lambda: dict(r=jnrun()), dict(),
+              lambda d, a: L.pm_jn2018_run(C.byref(d["r"]), None)),
+      "twocol": (lambda: dict(r=twocol()), dict(),
+                 lambda d, a: L.pm_twocol_run(C.byref(d["r"]), None)),
+  }
+
+  def call(entry, edits):
+    make, args, fn = entries[entry]
+    d, args = make(), dict(args)
+    for path, v in edits.items():
+      if path.startswith("@"):
+        args[path[1:]] = v
+        continue
+      *head, leaf = path.split(".")
+      obj = d[head[0]]
+      for h in head[1:]:
+        obj = getattr(obj, h)
+      setattr(obj, leaf, v)
+    rc = fn(d, args)
+    return rc, L.pm_last_error().decode()
+
+  def empty(prefix, n_fields, **more):  # the batch with no members (and what follows from it)
+    e = {prefix + f: 0 for f in n_fields.split()}
+    e.update({prefix + k: v for k, v in more.items()})
+    return e
+
+  E_JN = empty("jn.", "n cols.ncols ml.n")
+  E_RUN = dict(empty("r.jn.", "n cols.ncols ml.n"), **{"r.tw.n": 0, "r.so.n": 0})
+  E_TWOCOL = empty("r.", "tw.n cols.ncols")
+  rows = [
+      # ---- pm_thermwind_update
+      ("tw", {"tw.n": -1}, EINVAL, "shape"),
+      ("tw", {"tw.nz": 1}, EINVAL, "nz=1"),
+      ("tw", {"tw.nz": 1025}, EINVAL, "nz=1025"),
+      ("tw", {"tw.n": 0, "tw.nz": 1025}, EINVAL, "nz=1025"),
+      ("tw", {"tw.n": 0, "tw.nz": 2}, OK, ""),
+      ("tw", {"tw.n": 0, "tw.nz": 1024}, OK, ""),
+      ("tw", {"tw.n": 0, "tw.z": None, "tw.b1": None, "tw.b2": None, "tw.f": None, "tw.Psi": None}, OK, ""),
+      ("tw", {"@ops": 0}, EINVAL, "ops"),
+      ("tw", {"@ops": 16}, EINVAL, "ops"),
+      ("tw", {"@ops": 4}, EINVAL, "PM_TW_PSIB"),
+      ("tw", {"tw.nb": 0}, EINVAL, "nb"),
+      ("tw", {"tw.n": 0, "tw.nb": 0}, EINVAL, "nb"),
+      ("tw", {"tw.n": 0, "tw.nb": 0, "@ops": 1}, OK, ""),
+      ("tw", {"tw.z": None}, EINVAL, "NULL"),
+      ("tw", {"tw.b1": None}, EINVAL, "NULL"),
+      ("tw", {"tw.b2": None}, EINVAL, "NULL"),
+      ("tw", {"tw.Psi": None}, EINVAL, "NULL"),
+      ("tw", {"tw.f": None}, EINVAL, "NULL"),
+      # ---- pm_psi_so_update
+      ("so", {"so.n": -1}, EINVAL, "shape"),
+      ("so", {"so.nz": 1}, EINVAL, "nz=1"),
+      ("so", {"so.nz": 513}, EINVAL, "nz=513"),
+      ("so", {"so.ny": 1}, EINVAL, "ny=1"),
+      ("so", {"so.ny": 2049}, EINVAL, "ny=2049"),
+      ("so", {"so.n": 0, "so.nz": 2, "so.ny": 2}, OK, ""),
+      ("so", {"so.n": 0, "so.nz": 512, "so.ny": 2048}, OK, ""),
+      ("so", {"so.n": 0, "so.nz": 513}, EINVAL, "nz=513"),
+      ("so", {"so.n": 0, "so.z": None, "so.Psi": None, "so.bvp_refine": 1000}, OK, ""),
+      ("so", {"@ops": 0}, EINVAL, "ops"),
+      ("so", {"@ops": 4}, EINVAL, "ops"),
+      ("so", {"so.bvp_refine": -2}, EINVAL, "bvp_refine"),
+      ("so", {"so.bvp_refine": 257}, EINVAL, "bvp_refine"),
+      ("so", {"so.Psi": None}, EINVAL, "Psi"),
+      ("so", {"so.Psi_GM": None}, EINVAL, "Psi_GM"),
+  ] + [("so", {"so." + f: None}, EINVAL, "NULL") for f in "z y b bs tau KGM Psi_Ek".split()] + [
+      # ---- pm_so_ml_step
+      ("ml", {"ml.n": -1}, EINVAL, "shape"),
+      ("ml", {"ml.nz": 1}, EINVAL, "nz=1"),
+      ("ml", {"ml.nz": 4097}, EINVAL, "nz=4097"),
+      ("ml", {"ml.ny": 2}, EINVAL, "ny=2"),
+      ("ml", {"ml.ny": 2049}, EINVAL, "ny=2049"),
+      ("ml", {"ml.n": 0, "ml.nz": 2, "ml.ny": 3}, OK, ""),
+      ("ml", {"ml.n": 0, "ml.nz": 4096, "ml.ny": 2048}, OK, ""),
+      ("ml", {"ml.n": 0, "ml.ny": 2}, EINVAL, "ny=2"),
+      ("ml", {"ml.n": 0, "ml.y": None, "ml.bs": None}, OK, ""),
+  ] + [("ml", {"ml." + f: None}, EINVAL, "NULL")
+       for f in "y bs b_basin Psi_b surflux rest_mask b_rest".split()] + [
+      # ---- pm_so_tw_update
+      ("so_tw", {"so.n": 3}, EINVAL, "inconsistent"),
+      ("so_tw", {"tw.n": 3}, EINVAL, "inconsistent"),
+      ("so_tw", {"so.nz": 99}, EINVAL, "inconsistent"),
+      ("so_tw", {"so.n": -1, "tw.n": -1}, EINVAL, "inconsistent"),
+      ("so_tw", {"so.nz": 1, "tw.nz": 1}, EINVAL, "pm_so_tw_update"),
+      ("so_tw", {"so.nz": 257, "tw.nz": 257}, EINVAL, "nz"),
+      ("so_tw", {"so.ny": 1}, EINVAL, "pm_so_tw_update"),
+      ("so_tw", {"so.ny": 2049}, EINVAL, "pm_so_tw_update"),
+      ("so_tw", {"tw.nb": 0}, EINVAL, "pm_so_tw_update"),
+      ("so_tw", {"tw.nb": 0, "@ops": 1}, EINVAL, "pm_so_tw_update"),
+      ("so_tw", {"so.flags": _lib.PM_SO_HAS_C}, EINVAL, "smoother"),
+      ("so_tw", {"@ops": 0}, EINVAL, "ops"),
+      ("so_tw", {"@ops": 16}, EINVAL, "ops"),
+      ("so_tw", {"@ops": 4}, EINVAL, "ops"),
+      ("so_tw", {"so.n": 0, "tw.n": 0, "so.nz": 2, "tw.nz": 2, "so.ny": 2, "tw.nb": 1}, OK, ""),
+      ("so_tw", {"so.n": 0, "tw.n": 0, "so.nz": 256, "tw.nz": 256, "so.ny": 2048}, OK, ""),
+      ("so_tw", {"so.n": 0, "tw.n": 0, "so.bvp_refine": 1000, "so.z": None, "tw.z": None}, OK, ""),
+      ("so_tw", {"so.n": 0, "tw.n": 0, "so.flags": _lib.PM_SO_HAS_C}, EINVAL, "smoother"),
+      ("so_tw", {"tw.f": None}, EINVAL, "pm_thermwind"),
+  ] + [("so_tw", {"so." + f: None}, EINVAL, "pm_psi_so")
+       for f in "z y b bs tau KGM Psi Psi_Ek Psi_GM".split()] + [
+      ("so_tw", {"tw." + f: None}, EINVAL, "pm_thermwind") for f in "z b1 b2 Psi".split()] + [
+      # ---- pm_jn2018_steps (an empty batch still names its arrays)
+      ("steps", {"jn.n": -1}, EINVAL, "inconsistent"),
+      ("steps", {"jn.n": 3}, EINVAL, "inconsistent"),
+      ("steps", {"jn.cols.ncols": 5}, EINVAL, "inconsistent"),
+      ("steps", {"jn.ml.n": 3}, EINVAL, "inconsistent"),
+      ("steps", {"jn.ml.nz": 99}, EINVAL, "inconsistent"),
+      ("steps", {"jn.cols.nz": 1, "jn.ml.nz": 1}, EINVAL, "nz=1"),
+      ("steps", {"jn.cols.nz": 257, "jn.ml.nz": 257}, EINVAL, "nz=257"),
+      ("steps", {"jn.ml.ny": 2}, EINVAL, "ny=2"),
+      ("steps", {"jn.ml.ny": 2049}, EINVAL, "ny=2049"),
+      ("steps", {"jn.cols.nsel": 1}, EINVAL, "nsel"),
+      ("steps", {"jn.cols.ksel": None}, EINVAL, ".cols has a NULL"),
+      ("steps", {"@nsteps": -1}, EINVAL, "nsteps"),
+      ("steps", {"@nsteps": 0}, OK, ""),
+      ("steps", dict(E_JN), OK, ""),
+      ("steps", dict(E_JN, **{"jn.cols.nz": 2, "jn.ml.nz": 2, "jn.ml.ny": 3}), OK, ""),
+      ("steps", dict(E_JN, **{"jn.cols.nz": 256, "jn.ml.nz": 256, "jn.ml.ny": 2048}), OK, ""),
+      ("steps", dict(E_JN, **{"jn.wA": None}), EINVAL, "NULL"),
+  ] + [("steps", {"jn.cols." + f: None}, EINVAL, ".cols has a NULL")
+       for f in "z b kappa area dAkappa bs bbot N2min".split()] + [
+      ("steps", {"jn." + f: None}, EINVAL, "NULL") for f in "wA Psi_SO Psi_res_b Psi_res_n".split()] + [
+      ("steps", {"jn.ml." + f: None}, EINVAL, ".ml has a NULL")
+      for f in "y bs surflux rest_mask b_rest".split()] + [
+      # ---- pm_jn2018_run
+      ("run", {"r.jn.n": -1}, EINVAL, "inconsistent"),
+      ("run", {"r.jn.cols.ncols": 5}, EINVAL, "inconsistent"),
+      ("run", {"r.jn.ml.n": 3}, EINVAL, "inconsistent"),
+      ("run", {"r.jn.ml.nz": 99}, EINVAL, "inconsistent"),
+      ("run", {"r.tw.n": 3}, EINVAL, "inconsistent"),
+      ("run", {"r.tw.nz": 99}, EINVAL, "inconsistent"),
+      ("run", {"r.so.n": 3}, EINVAL, "inconsistent"),
+      ("run", {"r.so.nz": 99}, EINVAL, "inconsistent"),
+      ("run", {"r.so.ny": 39}, EINVAL, "inconsistent"),
+      ("run", {"r.jn.hints": 0}, EINVAL, "PM_JN_UNIFORM_AREA"),
+      ("run", {"r.jn.ml.status": None}, EINVAL, "ml.status"),
+      ("run", {"r.jn.ml.ny": 65, "r.so.ny": 65}, EINVAL, "ny"),
+      ("run", {"r.jn.ml.ny": 2, "r.so.ny": 2}, EINVAL, "ml"),
+      ("run", {"r.jn.cols.nz": 3, "r.jn.ml.nz": 3, "r.tw.nz": 3, "r.so.nz": 3}, EINVAL, "nz"),
+      ("run", {"r.jn.cols.nz": 257, "r.jn.ml.nz": 257, "r.tw.nz": 257, "r.so.nz": 257}, EINVAL, "nz"),
+      ("run", {"r.jn.cols.nz": 50, "r.jn.ml.nz": 50, "r.tw.nz": 50, "r.so.nz": 50}, EINVAL,
+       "not supported"),
+      ("run", {"r.jn.cols.nsel": 1}, EINVAL, "nsel"),
+      ("run", {"r.tw.nb": 0}, EINVAL, "tw"),
+      ("run", {"r.tw.b1_mid": A}, EINVAL, "tw"),
+      ("run", {"r.tw.b2_mid": A}, EINVAL, "tw"),
+      ("run", {"r.so.flags": _lib.PM_SO_HAS_C}, EINVAL, "smoother"),
+      ("run", {"r.sched.n_first": -1}, EINVAL, "schedule"),
+      ("run", {"r.sched.n_updates": -1}, EINVAL, "schedule"),
+      ("run", {"r.sched.m_steps": -1}, EINVAL, "schedule"),
+      ("run", {"r.sched.n_last": -1}, EINVAL, "schedule"),
+      ("run", {"r.sched.n_first": 0, "r.sched.n_updates": 0}, OK, ""),
+      ("run", {"r.sched.n_first": 0, "r.sched.n_updates": 0, "r.tw.z": None}, EINVAL, "tw"),
+      ("run", dict(E_RUN), OK, ""),
+      ("run", dict(E_RUN, **{"r.so.Psi": None}), EINVAL, "so"),
+      ("run", dict(E_RUN, **{"r.jn.cols.nz": 4, "r.jn.ml.nz": 4, "r.tw.nz": 4, "r.so.nz": 4,
+                             "r.jn.ml.ny": 3, "r.so.ny": 3, "r.tw.nb": 1}), OK, ""),
+      ("run", dict(E_RUN, **{"r.jn.cols.nz": 256, "r.jn.ml.nz": 256, "r.tw.nz": 256, "r.so.nz": 256,
+                             "r.jn.ml.ny": 64, "r.so.ny": 64}), OK, ""),
+  ] + [("run", {"r.jn.cols." + f: None}, EINVAL, "jn.cols has a NULL")
+       for f in "z b kappa area dAkappa bs bbot N2min ksel".split()] + [
+      ("run", {"r.jn." + f: None}, EINVAL, "jn has a NULL") for f in "wA Psi_SO Psi_res_b Psi_res_n".split()] + [
+      ("run", {"r.jn.ml." + f: None}, EINVAL, "jn.ml has a NULL")
+      for f in "y bs surflux rest_mask b_rest".split()] + [
+      ("run", {"r.tw." + f: None}, EINVAL, "tw has a NULL") for f in "z b1 b2 f Psi".split()] + [
+      ("run", {"r.so." + f: None}, EINVAL, "so has a NULL")
+      for f in "z y b bs tau KGM Psi Psi_Ek Psi_GM".split()] + [
+      # ---- pm_twocol_run
+      ("twocol", {"r.tw.n": -1}, EINVAL, "inconsistent"),
+      ("twocol", {"r.tw.n": 3}, EINVAL, "inconsistent"),
+      ("twocol", {"r.cols.ncols": 5}, EINVAL, "inconsistent"),
+      ("twocol", {"r.tw.nz": 99}, EINVAL, "inconsistent"),
+      ("twocol", {"r.cols.nz": 3, "r.tw.nz": 3}, EINVAL, "nz"),
+      ("twocol", {"r.cols.nz": 257, "r.tw.nz": 257}, EINVAL, "nz"),
+      ("twocol", {"r.cols.nz": 50, "r.tw.nz": 50}, EINVAL, "not supported"),
+      ("twocol", {"r.tw.nb": 0}, EINVAL, "pm_twocol_run"),
+      ("twocol", {"r.cols.nsel": 0}, EINVAL, "nsel"),
+      ("twocol", {"r.cols.nsel": 3}, EINVAL, "nsel"),
+      ("twocol", {"r.cols.nsel": 2, "r.cols.ksel": None}, EINVAL, "ksel"),
+      ("twocol", {"r.sched.n_first": -1}, EINVAL, "schedule"),
+      ("twocol", {"r.sched.n_updates": -1}, EINVAL, "schedule"),
+      ("twocol", {"r.sched.m_steps": -1}, EINVAL, "schedule"),
+      ("twocol", {"r.sched.n_last": -1}, EINVAL, "schedule"),
+      ("twocol", {"r.sched.n_first": 0, "r.sched.n_updates": 0, "r.tw.z": None, "r.cols.z": None,
+                  "r.wA": None}, OK, ""),
+      ("twocol", dict(E_TWOCOL, **{"r.tw.z": None, "r.cols.z": None, "r.wA": None}), OK, ""),
+      ("twocol", dict(E_TWOCOL, **{"r.cols.nz": 4, "r.tw.nz": 4, "r.tw.nb": 1}), OK, ""),
+      ("twocol", dict(E_TWOCOL, **{"r.cols.nz": 256, "r.tw.nz": 256, "r.cols.nsel": 2}), OK, ""),
+      ("twocol", dict(E_TWOCOL, **{"r.cols.nz": 257, "r.tw.nz": 257}), EINVAL, "nz"),
+      ("twocol", {"r.tw.b1_mid": A}, EINVAL, "pm_twocol_run"),
+      ("twocol", {"r.tw.b2_mid": A}, EINVAL, "pm_twocol_run"),
+      ("twocol", {"r.tw.Psi_SO": A}, EINVAL, "pm_twocol_run"),
+      ("twocol", {"r.wA": None}, EINVAL, "tw has a NULL"),
+  ] + [("twocol", {"r.cols." + f: None}, EINVAL, "cols has a NULL")
+       for f in "z b kappa area dAkappa bs bbot N2min flags".split()] + [
+      ("twocol", {"r.tw." + f: None}, EINVAL, "tw has a NULL")
+      for f in "z b1 b2 f Psi wA1 wA2".split()]
+  bad = []
+  for entry, edits, want, word in rows:
+    rc, msg = call(entry, edits)
+    if rc != want or (want != OK and word not in msg):
+      bad.append((entry, edits, want, word, rc, msg))
+  assert not bad, bad
+
+  # the descriptor itself missing
+  t, s = tw(), so()
+  assert L.pm_thermwind_update(None, 7, None) == EINVAL
+  assert L.pm_psi_so_update(None, 3, None) == EINVAL
+  assert L.pm_so_ml_step(None, 1., None) == EINVAL
+  assert L.pm_so_tw_update(None, C.byref(t), 7, None) == EINVAL
+  assert L.pm_so_tw_update(C.byref(s), None, 7, None) == EINVAL
+  assert L.pm_jn2018_steps(None, 1., 1, None) == EINVAL
+  assert L.pm_jn2018_run(None, None) == EINVAL
+  assert L.pm_twocol_run(None, None) == EINVAL
+
+  # pm_run_lds_bytes: bad arguments are refused, an unsupported shape is reported as 0 bytes
+  nbytes = C.c_size_t(7)
+  assert L.pm_run_lds_bytes(0, 100, 50, 0, None) == EINVAL
+  assert L.pm_run_lds_bytes(2, 100, 50, 0, C.byref(nbytes)) == EINVAL
+  assert L.pm_run_lds_bytes(-1, 100, 50, 0, C.byref(nbytes)) == EINVAL
+  for kind, nz, nb, ny, some in [(0, 100, 50, 0, True), (0, 65, 1, 0, True), (0, 128, 50, 0, True),
+                                 (0, 193, 50, 0, True), (0, 256, 50, 0, True), (0, 64, 50, 0, False),
+                                 (0, 129, 50, 0, False), (0, 192, 50, 0, False), (0, 257, 50, 0, False),
+                                 (0, 100, 0, 0, False), (1, 100, 50, 40, True), (1, 100, 50, 3, True),
+                                 (1, 100, 50, 64, True), (1, 100, 50, 2, False), (1, 100, 50, 65, False),
+                                 (1, 64, 50, 40, False), (1, 100, 0, 40, False)]:
+    assert L.pm_run_lds_bytes(kind, nz, nb, ny, C.byref(nbytes)) == OK
+    assert (nbytes.value > 0) == some, (kind, nz, nb, ny, nbytes.value)
+
+
 def test_column_kernel_name_follows_the_launch_plan():
   """pm_column_kernel_name names the instantiation pm_column_steps launches, read off the call
   alone: one case per row of the launch plan (column.hip.h, column_plan) and both sides of each

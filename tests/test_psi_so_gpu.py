@@ -386,7 +386,7 @@ def test_gm_adaptive_mesh_tall_grid_vs_oracle(gpu):
   assert seen >= 3
 
 
-def test_gm_adaptive_mesh_beyond_the_register_solver(gpu, monkeypatch):
+def test_gm_adaptive_mesh_beyond_the_register_solver(gpu):
   """A thin GM boundary layer (c = 0.02) drives solve_bvp beyond the 256 nodes the
   register-resident solver follows: the first launch flags the member (status bit 3), the
   follow-up launch redoes exactly the flagged members with the general solver (meshes up to
@@ -398,16 +398,14 @@ def test_gm_adaptive_mesh_beyond_the_register_solver(gpu, monkeypatch):
   cs = np.array([0.1, 0.02, 0.1, 0.01])  # members 1 and 3 overflow, 0 and 2 do not
   ref = [O.psi_so_solve(z, y, m["b_basin0"], m["bs_SO"], m["tau"], c=c, **kw)[2] for c in (0.1, 0.02, 0.01)]
 
-  def run(c):
-    t = gpu.PsiSOBatch(z, y, 3, tau=m["tau"], c=c, **kw)
+  def run(c, **more):
+    t = gpu.PsiSOBatch(z, y, 3, tau=m["tau"], c=c, **more, **kw)
     t.update(DeviceArray.from_host(np.stack([m["b_basin0"]] * 3)),
              DeviceArray.from_host(np.stack([m["bs_SO"]] * 3)))
     return t.Psi_GM.download(), t.status.download()
 
-  monkeypatch.setenv("PYMOC_SO_NO_FIXUP", "1")
-  GM, st = run(0.02)
+  GM, st = run(0.02, fixup=False)
   assert np.all(st & 8 == 8) and relerr(GM[0], ref[1]) > 1e-8  # flagged, last mesh's solution
-  monkeypatch.delenv("PYMOC_SO_NO_FIXUP")
   for c, r in zip((0.1, 0.02, 0.01), ref):
     GM, st = run(c)
     assert np.all(st & 10 == 0), c
