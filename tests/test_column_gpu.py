@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from column_plan_cases import _extreme_cases
 from conftest import load_golden
 from pymoc_amd import configs
 
@@ -233,34 +234,6 @@ def test_streaming_kernel_large_ensemble_bitwise(gpu, nz, nsteps):
                                    bzbot=None if np.isnan(bzbot[sl][j]) else bzbot[sl][j],
                                    N2min=c["N2min"][sl][j])
     assert np.array_equal(b[sl], ref), lo
-
-
-def _extreme_cases(c, N):
-  """Per-column edits of a config-2 ensemble that leave the window of the exact-division
-  shortcuts (common.hip.h: 2^-200 <= |x| <= 2^200 or 0): returns (b0, wA, bs, bbot, kinds)."""
-  rng = np.random.default_rng(17)
-  b0, wA, bs, bbot = c["b0"].copy(), c["wA"].copy(), c["bs"].copy(), np.array(c["bbot"], dtype=float) + np.zeros(N)
-  kinds = rng.integers(0, 8, N)
-  nz = b0.shape[1]
-  for m in range(N):
-    k = kinds[m]
-    if k == 1:    # the whole column scaled down by 2^-1000 (forcing too: CFL unchanged)
-      s = 2.0**-1000
-      b0[m] *= s; bs[m] *= s; bbot[m] *= s
-    elif k == 2:  # ... scaled up by 2^+900
-      s = 2.0**900
-      b0[m] *= s; bs[m] *= s; bbot[m] *= s
-    elif k == 3:  # an infinite interior level
-      b0[m, nz // 2] = np.inf
-    elif k == 4:  # a NaN next to the top, a -inf next to the bottom
-      b0[m, nz - 2] = np.nan
-      b0[m, 1] = -np.inf
-    elif k == 5:  # subnormal forcing
-      wA[m] *= 2.0**-1060
-    elif k == 6:  # buoyancy differences that round into the subnormal range
-      b0[m] = b0[m] * 2.0**-1015
-      bs[m] *= 2.0**-1015; bbot[m] *= 2.0**-1015
-  return b0, wA, bs, bbot, kinds
 
 
 @pytest.mark.parametrize("G", [16, 64])

@@ -510,6 +510,38 @@ def test_column_kernel_name_follows_the_launch_plan():
   assert buf.value == b"k_column_steps<64,1,0,false,false>"
 
 
+def test_every_launch_plan_row_has_a_whole_batch_oracle_case():
+  """tests/column_plan_cases.py, the table tests/test_column_plan_gpu.py runs on the device, holds
+  every row of PM_COLUMN_KERNELS (a row added without a numeric case fails here), each entry's
+  call selects the instantiation the entry names, and the rows differ in the template arguments
+  behind the shape.  The planted columns cover every kind at every slot of a wave."""
+  from pymoc_amd import _lib
+  import column_plan_cases as T
+  text = open(os.path.join(ROOT, "pymoc_amd", "csrc", "column.hip.h")).read()
+  rows = re.findall(r"X\((CK_[A-Z0-9_]+),", text)
+  assert len(rows) == len(set(rows)) >= 17
+  assert {c.id for c in T.CASES} == set(rows)
+  assert len({T.label(c) for c in T.CASES}) == len(T.CASES)
+  args = {}
+  for c in T.CASES:
+    d, wA, vdx = T.stand_in_call(c)
+    buf = ctypes.create_string_buffer(96)
+    for n in ((2, 1) if c.nsteps == 2 else (c.nsteps,)):  # (two steps also run as 1 + 1)
+      rc = _lib.lib.pm_column_kernel_name(ctypes.byref(d), wA, vdx, n, T.op_bits(c), c.lanes, buf, 96)
+      assert rc == _lib.PM_OK, _lib.lib.pm_last_error()
+      assert buf.value.decode() == c.name, T.label(c)
+    kernel, targs = re.fullmatch(r"(k_column_\w+)<(.*)>", c.name).groups()
+    shape = 1 if kernel == "k_column_stream" else 2  # <P, ...> / <G, P, ...>
+    args.setdefault(c.id, set()).add((kernel, ",".join(targs.split(",")[shape:])))
+  assert all(len(v) == 1 for v in args.values()), args
+  assert len({next(iter(v)) for v in args.values()}) == len(rows), args
+  for ncols in {c.ncols for c in T.CASES}:
+    cols, kinds, period = T.planted_columns(ncols)
+    assert period % 8 == 0 and kinds[cols == 0] == 3 and kinds[cols == ncols - 1] == 4
+    for k in range(8):
+      assert set(cols[kinds == k] % 8) == set(range(8)), (ncols, k)
+
+
 def test_product_does_not_import_oracle():
   pkg = os.path.join(ROOT, "pymoc_amd")
   for dirpath, _, files in os.walk(pkg):
