@@ -735,6 +735,69 @@ typedef struct pm_sections {
 
 int pm_sections_grid(const pm_sections *sec, pm_stream_t stream);
 
+/* ------------------------------------------------------------------ overturning sections
+ * The three fields the reference's figure script plots, examples/Plot_overturning.py:73-92, for
+ * every member of an ensemble: the depth-space (psi_z), isopycnal (psi_b) and residual (psi_res)
+ * overturning on the section [nrows][nz] assembled from the channel (ny rows), the basin (n_basin
+ * rows, every one the basin profile) and the north (n_north rows), nrows = ny + n_basin + n_north:
+ *   row 0                 zero in all three fields (the script's loop starts at 1)
+ *   channel rows >= 1     psi_res = psi_z = np.interp(bnew[iy], b_basin, Psi_SO)           (:79-80)
+ *                         psi_b[k] = Psi_SO[k] where b_basin[k] < bs_SO[iy], else 0        (:81)
+ *   basin rows            psi_res = psi_b = (c1[iy]*psibz1 + c2[iy]*Psi_SO)/lbasin         (:84, :86)
+ *                         psi_z = (c1[iy]*Psi + c2[iy]*Psi_SO)/lbasin                      (:85)
+ *   north rows            psi_res = np.interp(bnew[iy], bgrid, psib)                       (:89)
+ *                         psi_z = (c3[iy]*Psi)/lnorth                                      (:90)
+ *                         psi_b[k] = psibz1[k] where b_basin[k] < bnew[iy][nz-1], else 0   (:91)
+ *   last row              psi_res = 0                                                      (:92)
+ * bnew = concatenate(bsouth, tile(b_basin), bnorth) (:71).  c1 = ynew - lchannel, c2 = lchannel +
+ * lbasin - ynew, c3 = lchannel + lbasin + lnorth - ynew are formed by the caller in the script's
+ * order (the row coordinate ynew itself is not needed here); a comparison with NaN is false.
+ * IEEE fp64 in the script's operation order, np.interp as in pm_sections_grid: bit-identical.
+ * Member m's row of an input starts `offset + m * stride` doubles into it (pm_rows), so rows of an
+ * ensemble's state and of the solvers' outputs are read in place; stride 0 shares one row.
+ * Per member and field the maximum and minimum over the section with the row-major index
+ * iy*nz + k of their first occurrence (np.argmax / np.argmin); a field that holds a NaN reports NaN
+ * and the first NaN's index for both.  Fields: PM_OVT_Z, PM_OVT_B, PM_OVT_RES.
+ * status bits: PM_OVT_NAN_SECTION bnew holds a NaN (a point where the reference's brenth raises:
+ * the script would have stopped), PM_OVT_BAD_BASIN b_basin is non-finite or not non-decreasing
+ * (np.interp's result then depends on its search order); such members get whatever the
+ * interpolation gives and do not disturb the others.
+ * Sizes: 2 <= nz, ny <= 1024, 1 <= nb <= 2048, n_basin, n_north >= 1, n_basin + n_north <= 1024.  */
+#define PM_OVT_Z 0
+#define PM_OVT_B 1
+#define PM_OVT_RES 2
+#define PM_OVT_NAN_SECTION 1
+#define PM_OVT_BAD_BASIN 2
+#define PM_OVT_MAX_LEVELS 1024
+#define PM_OVT_MAX_NB 2048
+typedef struct pm_rows {
+  const double *ptr;
+  int64_t offset, stride;     /* in doubles */
+} pm_rows;
+typedef struct pm_overturning {
+  int32_t n, nz, ny, nb;      /* members, levels, channel rows, isopycnal classes            */
+  int32_t n_basin, n_north;   /* basin and north rows (the script: 60 and 10)                */
+  int32_t reserved1, reserved2;
+  pm_rows b_basin;            /* [nz] raw basin buoyancy                                     */
+  pm_rows bs_SO;              /* [ny] raw channel surface buoyancy                           */
+  pm_rows Psi;                /* [nz] AMOC.Psi                                               */
+  pm_rows Psi_SO;             /* [nz] PsiSO.Psi                                              */
+  pm_rows bgrid;              /* [nb] AMOC.bgrid                                             */
+  pm_rows psib;               /* [nb] AMOC.Psib(nb)                                          */
+  pm_rows psibz1;             /* [nz] AMOC.Psibz(nb)[0]                                      */
+  pm_rows bsouth;             /* [ny][nz] channel section                                    */
+  pm_rows bnorth;             /* [n_north][nz] northern section                              */
+  const double *c1, *c2, *c3; /* [nrows] shared row coefficients                             */
+  double lbasin, lnorth;
+  double *psi_z, *psi_b, *psi_res; /* [n][nrows][nz] out, each may be NULL (not stored)      */
+  double *bnew;               /* [n][nrows][nz] out: the assembled section (may be NULL)     */
+  double *extrema;            /* [n][3][2] out: {max, min} of PM_OVT_Z / _B / _RES (may be NULL) */
+  int32_t *extrema_at;        /* [n][3][2] out: their indices iy*nz + k (may be NULL)        */
+  int32_t *status;            /* [n] out: PM_OVT_* bits (may be NULL)                        */
+} pm_overturning;
+
+int pm_overturning_sections(const pm_overturning *d, pm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Convergence check of an ensemble run to steady state (pymoc_amd.run_to_steady), ONE launch
  * over the n rows of the current batch.  Row m holds original member k = orig[m]; rows whose

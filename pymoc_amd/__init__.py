@@ -14,6 +14,7 @@ from .so_ml import SOMLBatch
 from .equilibrium import ColumnEquiBatch
 from .equi_column import EquiColumnBatch
 from .sections import SectionBatch
+from .overturning import OverturningSections
 from . import modules
 from . import utils
 from .modules import Column, Psi_Thermwind, Psi_SO, SO_ML, Equi_Column

@@ -155,6 +155,31 @@ class pm_sections(C.Structure):
   ]
 
 
+PM_OVT_Z, PM_OVT_B, PM_OVT_RES = 0, 1, 2
+PM_OVT_NAN_SECTION, PM_OVT_BAD_BASIN = 1, 2
+PM_OVT_MAX_LEVELS, PM_OVT_MAX_NB = 1024, 2048
+
+
+class pm_rows(C.Structure):
+  """Mirror of `struct pm_rows` (include/pymoc_hip.h)."""
+  _fields_ = [("ptr", c_dp), ("offset", C.c_int64), ("stride", C.c_int64)]
+
+
+class pm_overturning(C.Structure):
+  """Mirror of `struct pm_overturning` (include/pymoc_hip.h)."""
+  _fields_ = [
+      ("n", C.c_int32), ("nz", C.c_int32), ("ny", C.c_int32), ("nb", C.c_int32),
+      ("n_basin", C.c_int32), ("n_north", C.c_int32), ("reserved1", C.c_int32),
+      ("reserved2", C.c_int32),
+      ("b_basin", pm_rows), ("bs_SO", pm_rows), ("Psi", pm_rows), ("Psi_SO", pm_rows),
+      ("bgrid", pm_rows), ("psib", pm_rows), ("psibz1", pm_rows), ("bsouth", pm_rows),
+      ("bnorth", pm_rows), ("c1", c_dp), ("c2", c_dp), ("c3", c_dp),
+      ("lbasin", C.c_double), ("lnorth", C.c_double),
+      ("psi_z", c_dp), ("psi_b", c_dp), ("psi_res", c_dp), ("bnew", c_dp),
+      ("extrema", c_dp), ("extrema_at", c_dp), ("status", c_dp)
+  ]
+
+
 PM_PACK_MAX_ITEMS = 8
 
 
@@ -289,6 +314,7 @@ SIGNATURES = {
     "pm_selftest_so_scans": (C.c_int, [C.c_int32, C.c_uint64, C.POINTER(C.c_double),
                                        C.POINTER(C.c_int32)]),
     "pm_sections_grid": (C.c_int, [C.POINTER(pm_sections), C.c_void_p]),
+    "pm_overturning_sections": (C.c_int, [C.POINTER(pm_overturning), C.c_void_p]),
     "pm_steady_check": (C.c_int, [C.POINTER(pm_steady_check), C.c_void_p]),
 }
 
