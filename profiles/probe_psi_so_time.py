@@ -13,12 +13,12 @@ for refine in (8, -1):
   e.run(241)
   gpu.synchronize()
   for _ in range(3):
-    e.so.update(e._b_basin, e.bs_SO)
+    e.so.update(e.b_basin, e.bs_SO)
   gpu.synchronize()
   t0 = time.perf_counter()
   K = 50
   for _ in range(K):
-    e.so.update(e._b_basin, e.bs_SO)
+    e.so.update(e.b_basin, e.bs_SO)
   gpu.synchronize()
   el = (time.perf_counter() - t0) / K
   print("refine %3d: k_psi_so %.1f us per update of %d members" % (refine, el * 1e6, N))

@@ -14,7 +14,7 @@ out = (C.c_ulonglong * 16)()
 _lib.lib.pm_debug_prof(out)
 K = 20
 for _ in range(K):
-  e.so.update(e._b_basin, e.bs_SO)
+  e.so.update(e.b_basin, e.bs_SO)
 gpu.synchronize()
 _lib.lib.pm_debug_prof(out)
 v = np.array(list(out), dtype=np.float64)

@@ -12,7 +12,6 @@ N = int(os.environ.get("N", {3: 4096, 4: 8192, 5: 4096}[CONFIG]))
 if CONFIG == 5:
   e = gpu.JN2018Ensemble(configs.config5(N=N))
   e.run(361)
-  e._b_basin, e._b_north = e.cols.b.ptr, e.cols.b.ptr + e._off
 else:
   e = gpu.TwoColEnsemble(configs.config3(N=N) if CONFIG == 3 else configs.config4(N=N))
   e.run(241)
@@ -21,7 +20,7 @@ out = (C.c_ulonglong * 16)()
 _lib.lib.pm_debug_prof(out)
 K = 20
 for _ in range(K):
-  e.tw.update(e._b_basin, e._b_north, store_psib=False)
+  e.tw.update(e.b_basin, e.b_north, store_psib=False)
 gpu.synchronize()
 _lib.lib.pm_debug_prof(out)
 v = np.array(list(out), dtype=np.float64)

@@ -36,7 +36,7 @@ if CONFIG == 5:
   e = gpu.JN2018Ensemble(configs.config5(N=N))
   e.run(361)
   gpu.synchronize()
-  b_basin, b_north = e.cols.b.ptr, e.cols.b.ptr + e._off
+  b_basin, b_north = e.b_basin, e.b_north
   e.so.update(b_basin, e.ml.bs); gpu.synchronize(); timeline("k_psi_so", N)
   e.tw.update(b_basin, b_north, store_psib=False); gpu.synchronize(); timeline("k_thermwind", N)
   e.run(35); gpu.synchronize()   # to the MOC boundary: the next launch fuses a whole interval
@@ -47,5 +47,5 @@ else:
   e.run(241)
   gpu.synchronize()
   if e.so is not None:
-    e.so.update(e._b_basin, e.bs_SO); gpu.synchronize(); timeline("k_psi_so", N)
-  e.tw.update(e._b_basin, e._b_north, store_psib=False); gpu.synchronize(); timeline("k_thermwind", N)
+    e.so.update(e.b_basin, e.bs_SO); gpu.synchronize(); timeline("k_psi_so", N)
+  e.tw.update(e.b_basin, e.b_north, store_psib=False); gpu.synchronize(); timeline("k_thermwind", N)

@@ -133,7 +133,7 @@ class JN2018Diagnostics(object):
       return
     e = self.ens
     self.ts.append(dict(AMOC=e.tw.Psi, AMOC_b=e.tw.psib, bgrid=e.tw.bgrid,
-                        b_basin=e.cols.b.ptr, b_north=e.cols.b.ptr + e._off,
+                        b_basin=e.b_basin, b_north=e.b_north,
                         bs_SO=e.ml.bs, Psi_SO=e.so.Psi), k=k)
 
   def __getattr__(self, name):

@@ -11,11 +11,14 @@ classes here reproduce those loops' order of operations and cadence exactly:
                            examples/example_twocol_plusSO.py:99-115 (config 4, with_so)
 Each member is independent; `cfg` is a dict from `pymoc_amd.configs`.
 """
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
-from .columns import ColumnBatch
-from .device import DeviceArray, _sh, launch_span
+from ._lib import check, lib
+from .columns import ColumnBatch, _HINT_DIV3_OFF, device_reciprocals_exact, div3_proven
+from .device import DeviceArray, Event, Graph, Stream, _sh, launch_span
 from .equilibrium import ColumnEquiBatch
 from .psi_so import PsiSOBatch
 from .sharding import DiagnosticGather
@@ -39,9 +42,8 @@ def _rows(v, n, nz):
 def _run_fits(kind, nz, nb, ny):
   """Do the phases of a persistent run kernel (kind 0: pm_twocol_run, 1: pm_jn2018_run) fit the
   160 KB of LDS of a CU at 16 members per block?"""
-  import ctypes as C
   nbytes = C.c_size_t(0)
-  _lib.check(_lib.lib.pm_run_lds_bytes(int(kind), int(nz), int(nb), int(ny), C.byref(nbytes)))
+  check(lib.pm_run_lds_bytes(int(kind), int(nz), int(nb), int(ny), C.byref(nbytes)))
   return 0 < nbytes.value <= 160 * 1024
 
 
@@ -85,7 +87,6 @@ class ColumnThermwindEnsemble(object):
     self._solve()
 
   def run(self, nsteps):
-    from .device import Graph
     remaining = int(nsteps)
     while self._use_graph and remaining >= self.GRAPH_STEPS:
       if self._graph is None:
@@ -132,8 +133,8 @@ class EquiIterationEnsemble(object):
   def iterate(self, niter=1):
     for _ in range(int(niter)):
       self.eq.solve(self.wA)
-      _lib.check(_lib.lib.pm_axpby(self.n * self.nz, self.keep, self.b1.ptr, self.relax,
-                                   self.eq.b.ptr, self.b1.ptr, _sh(self.stream)))
+      check(lib.pm_axpby(self.n * self.nz, self.keep, self.b1.ptr, self.relax, self.eq.b.ptr,
+                         self.b1.ptr, _sh(self.stream)))
       self._solve()
 
   def state(self):
@@ -141,9 +142,159 @@ class EquiIterationEnsemble(object):
                 Psi=self.tw.Psi.download(stream=self.stream))
 
 
-class TwoColEnsemble(object):
+class CoupledEnsemble(object):
+  """What TwoColEnsemble, JN2018Ensemble and TwoBasinEnsemble share: the diagnostic gather, the
+  downloads of `state()`, two launches side by side, the cadence of the loop, how a per-member
+  `cfg` key is read, and the restart protocol `run_to_steady` drives.
+
+  A driver's columns are stacked in NGROUPS groups of n rows (`cols.b`, `wA`); its constructor
+  makes the views of those groups once (`b_basin`, `wA_north`, ...: DeviceArray.view) and every
+  launch, gather and check takes them from there.
+
+  MEMBER_KEYS is the single statement of how a per-member `cfg` key is read -- by the
+  constructor (`read`), by a restriction to some members (`restrict`) and by the tests:
+    ("vec",)       a scalar is shared; an array has the member axis first ((n,) or (n, ...))
+    ("rows", axis) a profile on cfg[axis]: 2-D is per member; 1-D of length n is one value per
+                   member, repeated along the axis -- unless n equals the axis length, when it is
+                   the shared profile; a scalar or any other 1-D array is shared
+    ("2d", axis)   a profile on cfg[axis]: 2-D is per member, anything else is shared
+  None: the driver's constructor reads its cfg by itself and cannot be restarted on a subset."""
+
+  NGROUPS = 2
+  FIELDS = ("b_basin", "b_north", "Psi", "Psi_SO")
+  MEMBER_KEYS = None
+  RESTART_PHASE = None  # the steps s = RESTART_PHASE (mod MOC_up_iters) can be restarted from
+
+  @classmethod
+  def members(cls, cfg):
+    return np.atleast_2d(cfg['b_basin0']).shape[0]
+
+  @classmethod
+  def _rule(cls, cfg, key, n):
+    """(the value as float64, the length of its rows or None, is its first axis the members?)"""
+    rule = cls.MEMBER_KEYS[key]
+    a = np.asarray(cfg[key], dtype=np.float64)
+    if rule[0] == "vec":
+      return a, None, a.ndim >= 1
+    nlev = np.asarray(cfg[rule[1]]).size
+    return a, nlev, a.ndim == 2 or (rule[0] == "rows" and a.ndim == 1 and a.shape[0] == n and
+                                    n != nlev)
+
+  @classmethod
+  def read(cls, cfg, key, n):
+    """cfg[key] of an n-member cfg as an explicit [n, ...] array, by the key's rule."""
+    a, nlev, per_member = cls._rule(cfg, key, n)
+    if nlev is None:
+      return a if per_member else np.full(n, a)
+    if per_member:
+      return a if a.ndim == 2 else np.repeat(a[:, None], nlev, axis=1)
+    return np.broadcast_to(a, (n, nlev)).copy()
+
+  @classmethod
+  def restrict(cls, cfg, keep):
+    """`cfg` restricted to members `keep` (indices into its current members): a per-member key is
+    expanded to explicit [n, ...] at the current n, then indexed -- so a 1-D per-member array never
+    comes back as a length-nz vector that would be read as a profile.  Shared keys, and keys the
+    constructor does not read per member, are passed on unchanged."""
+    n = cls.members(cfg)
+    keep = np.asarray(keep, dtype=np.int64)
+    out = dict(cfg)
+    for key in cls.MEMBER_KEYS:
+      if key in cfg and cls._rule(cfg, key, n)[2]:
+        out[key] = cls.read(cfg, key, n)[keep]
+    return out
+
+  @staticmethod
+  def _check_arith(arith):
+    if arith not in ("exact", "contracted"):
+      raise ValueError("arith must be 'exact' or 'contracted'")
+    return arith
+
+  def _init_gather(self, comm, n_total, keep_history, gather, gather_overlap):
+    self.diag = None
+    if comm is not None or keep_history:
+      self.diag = DiagnosticGather(comm, self.n, self.n if n_total is None else n_total,
+                                   [(k, self.nz) for k in self.FIELDS], stream=self.stream,
+                                   keep_history=keep_history, mode=gather, overlap=gather_overlap)
+
+  def fields(self):
+    """name -> DeviceArray of the entries of FIELDS (the two-column layout; without an SO channel
+    Psi_SO is a zero array)."""
+    return dict(b_basin=self.b_basin, b_north=self.b_north, Psi=self.tw.Psi,
+                Psi_SO=self.so.Psi if self.so is not None else self._zero_so)
+
+  def gather_diagnostics(self, step=None):
+    """Gather FIELDS of every rank's members (device buffers, one collective);
+    `self.diag.last()` returns the assembled host arrays."""
+    self.diag.gather(self.fields(), step=self.ii if step is None else step)
+
+  def _gather_if_due(self, step):
+    if self.diag is not None and self.diag.due(step, self.diag_iters):
+      self.gather_diagnostics(step)
+
+  def nonfinite_members(self):
+    nf = self.cols.get_nonfinite().reshape(self.NGROUPS, self.n)
+    return np.nonzero(np.bitwise_or.reduce(nf, axis=0))[0]
+
+  def _download(self, **arrays):
+    return {k: a.download(stream=self.stream) for k, a in arrays.items()}
+
+  def _side_by_side(self, side_fn, main_fn):
+    """side_fn(self._side) beside main_fn(self.stream): the side stream starts behind what
+    self.stream holds so far, and self.stream goes on only when both are done."""
+    self._ev_fork.record(self.stream)
+    self._side.wait(self._ev_fork)
+    side_fn(self._side)
+    self._ev_join.record(self._side)
+    main_fn(self.stream)
+    check(lib.pm_stream_wait_event(_sh(self.stream), self._ev_join.handle))
+
+  def _interval(self, remaining):
+    """The steps up to and including the next one an update follows (ii % M == 0), at most
+    `remaining`: they share one forcing, so they are one launch."""
+    nxt = self.ii if self.ii % self.M == 0 else (self.ii // self.M + 1) * self.M
+    return min(nxt - self.ii + 1, remaining)
+
+  def drift_fields(self):
+    """[(name, DeviceArray, row stride, len)] of the prognostic state: what drifts, and what a
+    restart carries over as the cfg's initial profiles `<name>0`."""
+    nz = self.nz
+    return [("b_basin", self.b_basin, nz, nz), ("b_north", self.b_north, nz, nz)]
+
+  def capture_fields(self):
+    """The drift fields, then the overturnings of the update at the restart point."""
+    nz = self.nz
+    f = self.drift_fields() + [("Psi", self.tw.Psi, nz, nz)]
+    return f + [("Psi_SO", self.so.Psi, nz, nz)] if self.so is not None else f
+
+  def at_restart_point(self):
+    """Bring the diagnostics to the state a restart at this step (= RESTART_PHASE mod M) has."""
+
+  def subset(self, keep, cfg, kw):
+    """A new ensemble of this class from members `keep` of this one (built from `cfg`, **kw) at
+    the same step, at a restart point: it continues bit-identically to these members here."""
+    keep = np.asarray(keep, dtype=np.int64)
+    cfg = self.restrict(cfg, keep)
+    for name, a, _, _ in self.drift_fields():
+      cfg[name + "0"] = a.download(stream=self.stream)[keep]
+    new = type(self)(cfg, **kw)
+    new.ii = self.ii
+    new.at_restart_point()
+    return new
+
+
+class TwoColEnsemble(CoupledEnsemble):
   """Basin + northern sinking column per member, coupled by the thermal-wind overturning
   mapped to isopycnal space every MOC_up_iters steps."""
+
+  # every key is read through `read`; tau / KGM go on to PsiSOBatch, which reads a 1-D array of
+  # length n as one value per member and a 2-D one as profiles on y: the "vec" rule
+  MEMBER_KEYS = dict(kappa=("rows", "z"), A_basin=("rows", "z"), A_north=("rows", "z"),
+                     bs=("vec",), bs_north=("vec",), bbot=("vec",), tau=("vec",), KGM=("vec",),
+                     bs_SO=("rows", "y"), b_basin0=("rows", "z"), b_north0=("rows", "z"))
+  # after the update that follows step s - 1 (example_twocol.py:85-96): the constructor's own
+  # update is the one at a restart
+  RESTART_PHASE = 1
 
   def __init__(self, cfg, stream=None, lanes_per_col=0, comm=None, n_total=None,
                diag_iters=None, keep_history=False, arith="exact", overlap_updates=False,
@@ -168,52 +319,40 @@ class TwoColEnsemble(object):
     `arith="contracted"`: the columns step in the opt-in tolerance mode (ColumnBatch.steps)."""
     z = cfg['z']
     nz = z.size
-    n = np.atleast_2d(cfg['b_basin0']).shape[0]
+    n = self.members(cfg)
+    rd = lambda key: self.read(cfg, key, n)  # noqa: E731
     self.n, self.nz = n, nz
     self.dt, self.M, self.nb = float(cfg['dt']), int(cfg['MOC_up_iters']), int(cfg['nb'])
-    self.lanes = lanes_per_col
-    self.arith = arith
-    self.stream = stream
+    self.lanes, self.arith, self.stream = lanes_per_col, arith, stream
     self.diag_iters = cfg.get('Diag_iters') if diag_iters is None else diag_iters
-    self.diag = None
     self.timer = None  # optional device.LaunchTimer: events around every launch of run()
-    if comm is not None or keep_history:
-      self.diag = DiagnosticGather(comm, n, n if n_total is None else n_total,
-                                   [(k, nz) for k in ('b_basin', 'b_north', 'Psi', 'Psi_SO')],
-                                   stream=stream, keep_history=keep_history, mode=gather,
-                                   overlap=gather_overlap)
-    kap = _rows(cfg['kappa'], n, nz)
+    self._init_gather(comm, n_total, keep_history, gather, gather_overlap)
+    kap = rd('kappa')
     # rows [0, n): basin columns, rows [n, 2n): northern columns
     self.cols = ColumnBatch(
-        z, np.concatenate([kap, kap]),
-        np.concatenate([_rows(cfg['A_basin'], n, nz), _rows(cfg['A_north'], n, nz)]),
-        np.concatenate([_rows(cfg['b_basin0'], n, nz), _rows(cfg['b_north0'], n, nz)]),
-        bs=np.concatenate([_vec(cfg['bs'], n), _vec(cfg['bs_north'], n)]),
-        bbot=np.concatenate([_vec(cfg['bbot'], n), _vec(cfg['bbot'], n)]),
+        z, np.concatenate([kap, kap]), np.concatenate([rd('A_basin'), rd('A_north')]),
+        np.concatenate([rd('b_basin0'), rd('b_north0')]),
+        bs=np.concatenate([rd('bs'), rd('bs_north')]), bbot=np.tile(rd('bbot'), 2),
         do_conv=np.concatenate([np.zeros(n, bool), np.ones(n, bool)]), stream=stream)
     self.tw = ThermwindBatch(z, n, f=cfg['f'], nb=self.nb, stream=stream, z_dev=self.cols.z)
     self.wA = DeviceArray.zeros((2 * n, nz), stream=stream)
-    self._off = n * nz * 8
+    self.b_basin, self.b_north = self.cols.b.view(0, n), self.cols.b.view(n, n)
+    self.wA_basin, self.wA_north = self.wA.view(0, n), self.wA.view(n, n)
     self.ii = 0
     self.so = None
     if 'y' in cfg and 'bs_SO' in cfg:  # example_twocol_plusSO.py:69-81
-      ny = cfg['y'].size
-      self.so = PsiSOBatch(z, cfg['y'], n, tau=cfg['tau'], KGM=cfg['KGM'], f=cfg['f'],
+      self.so = PsiSOBatch(z, cfg['y'], n, tau=rd('tau'), KGM=rd('KGM'), f=cfg['f'],
                            L=cfg['L'], c=cfg.get('c'), bvp_with_Ek=cfg.get('bvp_with_Ek', False),
                            bvp_refine=cfg.get('bvp_refine', 0), stream=stream,
                            z_dev=self.cols.z)
-      self.bs_SO = DeviceArray.from_host(_rows(cfg['bs_SO'], n, ny) if np.ndim(cfg['bs_SO']) == 1
-                                         else cfg['bs_SO'], stream=stream)
+      self.bs_SO = DeviceArray.from_host(rd('bs_SO'), stream=stream)
     self._zero_so = (DeviceArray.zeros((n, nz), stream=stream)
                      if self.so is None and self.diag is not None else None)
     self._overlap = self.so is not None and bool(overlap_updates)
     if self._overlap:
-      from .device import Stream, Event
-      self._side = Stream()
-      self._ev_fork, self._ev_join = Event(), Event()
+      self._side, self._ev_fork, self._ev_join = Stream(), Event(), Event()
     can_fuse = (self.so is None and arith == "exact" and self.cols.uniform_area and
-                not self.cols.has_bzbot and
-                _run_fits(0, nz, self.nb, 0))
+                not self.cols.has_bzbot and _run_fits(0, nz, self.nb, 0))
     if fused_run and not can_fuse:
       raise ValueError("fused_run needs: no SO channel, exact arithmetic, Area constant in z, no "
                        "bzbot, 4 <= nz <= 256 and the phases' LDS within 160 KB")
@@ -222,17 +361,11 @@ class TwoColEnsemble(object):
                        else None)
     self._update()  # AMOC.solve(); AMOC.Psibz() [; SO.solve()] on the initial profiles
 
-  # device views
-  @property
-  def _b_basin(self):
-    return self.cols.b.ptr
-
-  @property
-  def _b_north(self):
-    return self.cols.b.ptr + self._off
-
-  def _psi_so(self):
-    return self.so.Psi if self.so is not None else None
+  def _solve_so(self, stream):
+    self.so.stream = stream
+    with launch_span(self.timer, "k_psi_so", stream):
+      self.so.update(self.b_basin, self.bs_SO)
+    self.so.stream = self.stream
 
   def _update(self):
     # SO.solve() and AMOC.solve() both read basin.b only.  With the SO channel the two launches
@@ -241,28 +374,17 @@ class TwoColEnsemble(object):
     # wAb = (Psi_iso_b - SO.Psi)*1e6, wAN = -Psi_iso_n*1e6 themselves (PM_OP_WA_PSI) once both
     # are done -- the same operations as the thermal-wind launch's wA1 / wA2 epilogue.
     if self.so is not None and self._overlap:
-      self._ev_fork.record(self.stream)     # the columns' steps before this update
-      self._side.wait(self._ev_fork)
-      self.so.stream = self._side
-      with launch_span(self.timer, "k_psi_so", self._side):
-        self.so.update(self._b_basin, self.bs_SO)
-      self.so.stream = self.stream
-      self._ev_join.record(self._side)
-      with launch_span(self.timer, "k_thermwind", self.stream):
-        self.tw.update(self._b_basin, self._b_north, ops=_TW_ALL, store_psib=False)
-      if self.stream is not None:
-        self.stream.wait(self._ev_join)
-      else:
-        from ._lib import check, lib
-        check(lib.pm_stream_wait_event(None, self._ev_join.handle))
+      def thermwind(stream):
+        with launch_span(self.timer, "k_thermwind", stream):
+          self.tw.update(self.b_basin, self.b_north, ops=_TW_ALL, store_psib=False)
+      self._side_by_side(self._solve_so, thermwind)
       return
     if self.so is not None:
-      with launch_span(self.timer, "k_psi_so", self.stream):
-        self.so.update(self._b_basin, self.bs_SO)
+      self._solve_so(self.stream)
     with launch_span(self.timer, "k_thermwind", self.stream):
-      self.tw.update(self._b_basin, self._b_north, ops=_TW_ALL, store_psib=False,
-                     Psi_SO=self._psi_so(),
-                     wA1=self.wA.ptr, wA2=self.wA.ptr + self._off)
+      self.tw.update(self.b_basin, self.b_north, ops=_TW_ALL, store_psib=False,
+                     Psi_SO=self.so.Psi if self.so is not None else None,
+                     wA1=self.wA_basin, wA2=self.wA_north)
 
   def _steps(self, n):
     with launch_span(self.timer, "k_column_steps" if n >= 3 else "k_column_steps_short",
@@ -275,7 +397,6 @@ class TwoColEnsemble(object):
                       psi_forcing=(self.tw.psibz, self.so.Psi))
       return
     if self.so is not None and self._overlap:  # a launch of 1-2 steps: the forcing as an array
-      from ._lib import check, lib
       check(lib.pm_twocol_forcing(self.n, self.nz, self.tw.psibz.ptr, self.so.Psi.ptr,
                                   self.wA.ptr, _sh(self.stream)))
     self.cols.steps(self.wA, self.dt, n, lanes_per_col=self.lanes, arith=self.arith)
@@ -283,7 +404,6 @@ class TwoColEnsemble(object):
   def _run_fused(self, nsteps):
     """The same loop through pm_twocol_run: one launch per stretch that ends at a diagnostic
     gather (or at the end of the run)."""
-    import ctypes as C
     M, remaining = self.M, int(nsteps)
     while remaining > 0:
       ii = self.ii
@@ -312,11 +432,11 @@ class TwoColEnsemble(object):
         end = k + 1 + sch.n_last
       d = _lib.pm_twocol_loop()
       d.cols = self.cols.descriptor()
-      d.tw = self.tw.descriptor(self._b_basin, self._b_north, wA1=self.wA.ptr,
-                                wA2=self.wA.ptr + self._off, store_psib=False)
+      d.tw = self.tw.descriptor(self.b_basin, self.b_north, wA1=self.wA_basin,
+                                wA2=self.wA_north, store_psib=False)
       d.wA, d.dt, d.sched, d.status = self.wA.ptr, self.dt, sch, self.run_status.ptr
       with launch_span(self.timer, "k_twocol_run", self.stream):
-        _lib.check(_lib.lib.pm_twocol_run(C.byref(d), _sh(self.stream)))
+        check(lib.pm_twocol_run(C.byref(d), _sh(self.stream)))
       remaining -= end - ii
       self.ii = end
       if gather_at is not None:
@@ -329,38 +449,24 @@ class TwoColEnsemble(object):
       return self._run_fused(nsteps)
     remaining = int(nsteps)
     while remaining > 0:
-      nxt = self.ii if self.ii % self.M == 0 else (self.ii // self.M + 1) * self.M
-      n = min(nxt - self.ii + 1, remaining)
+      n = self._interval(remaining)
       self._steps(n)
       self.ii += n
       remaining -= n
       if (self.ii - 1) % self.M == 0:
         self._update()
-        if self.diag is not None and self.diag.due(self.ii - 1, self.diag_iters):
-          self.gather_diagnostics(self.ii - 1)
-
-  def gather_diagnostics(self, step=None):
-    """All-gather {b_basin, b_north, Psi_AMOC, Psi_SO} of every rank's members (device
-    buffers, one collective); `self.diag.last()` returns the assembled host arrays."""
-    self.diag.gather(dict(b_basin=self._b_basin, b_north=self._b_north, Psi=self.tw.Psi,
-                          Psi_SO=self.so.Psi if self.so is not None else self._zero_so),
-                     step=self.ii if step is None else step)
+        self._gather_if_due(self.ii - 1)
 
   def state(self):
-    b = self.cols.get_b()
-    out = dict(b_basin=b[:self.n], b_north=b[self.n:], Psi=self.tw.Psi.download(stream=self.stream),
-               Psi_iso_b=self.tw.psibz1.download(stream=self.stream), Psi_iso_n=self.tw.psibz2.download(stream=self.stream))
+    out = self._download(b_basin=self.b_basin, b_north=self.b_north, Psi=self.tw.Psi,
+                         Psi_iso_b=self.tw.psibz1, Psi_iso_n=self.tw.psibz2)
     if self.so is not None:
-      out.update(Psi_SO=self.so.Psi.download(stream=self.stream), Psi_Ek=self.so.Psi_Ek.download(stream=self.stream),
-                 Psi_GM=self.so.Psi_GM.download(stream=self.stream))
+      out.update(self._download(Psi_SO=self.so.Psi, Psi_Ek=self.so.Psi_Ek,
+                                Psi_GM=self.so.Psi_GM))
     return out
 
-  def nonfinite_members(self):
-    nf = self.cols.get_nonfinite()
-    return np.nonzero(nf[:self.n] | nf[self.n:])[0]
 
-
-class JN2018Ensemble(object):
+class JN2018Ensemble(CoupledEnsemble):
   """run_JansenNadeau_2018.py with default flags: basin + north columns, thermal wind,
   SO channel overturning (no BVP smoother) and the SO mixed layer, with the script's
   per-step bottom-BC / bottom-boundary-layer diffusivity switching.
@@ -368,6 +474,18 @@ class JN2018Ensemble(object):
   Per step: BC switch -> both columns (convective adjustment on) -> mixed layer; every
   MOC_up_iters steps (before the step) the three diagnostics are refreshed.  With
   `use_graph` a whole MOC block is captured once into a hipGraph and replayed."""
+
+  # every key is read through `read`; tau / KGM go on to PsiSOBatch ("vec": as for
+  # TwoColEnsemble) and surflux / rest_mask / b_rest to SOMLBatch, which reads a 1-D array as the
+  # shared profile on y whatever its length: the "2d" rule, as np.broadcast_to does for the
+  # diffusivity profiles
+  MEMBER_KEYS = dict(kappa=("2d", "z"), kappaeff=("2d", "z"), A_basin=("rows", "z"),
+                     A_north=("rows", "z"), bs=("vec",), bs_north=("vec",), tau=("vec",),
+                     KGM=("vec",), surflux=("2d", "y"), rest_mask=("2d", "y"),
+                     b_rest=("2d", "y"), b_basin0=("rows", "z"), b_north0=("rows", "z"),
+                     bs_SO0=("rows", "y"))
+  # after step s's MOC update, before the step (run_JansenNadeau_2018.py:204-217)
+  RESTART_PHASE = 0
 
   def __init__(self, cfg, stream=None, lanes_per_col=0, use_graph=False, fused=None,
                comm=None, n_total=None, diag_iters=None, keep_history=False, arith="exact",
@@ -388,48 +506,40 @@ class JN2018Ensemble(object):
     PM_JN_SHARED_COEF); results are bit-identical either way.
     `split_lanes`: the fused loop steps both columns of a member together, one per half of the
     wavefront (PM_JN_SPLIT_LANES; bit-identical; measured a tie on config 5, hence opt-in)."""
-    if arith not in ("exact", "contracted"):
-      raise ValueError("arith must be 'exact' or 'contracted'")
-    self.arith = arith
+    self.arith = self._check_arith(arith)
     self.shared_coef = bool(shared_coef)
     self.split_lanes = bool(split_lanes)
-    import ctypes as C
-    from ._lib import pm_jn2018_bc
     z, y = cfg['z'], cfg['y']
     nz, ny = z.size, y.size
-    n = np.atleast_2d(cfg['b_basin0']).shape[0]
+    n = self.members(cfg)
+    rd = lambda key: self.read(cfg, key, n)  # noqa: E731
     self.n, self.nz, self.ny = n, nz, ny
     self.dt, self.M, self.nb = float(cfg['dt']), int(cfg['MOC_up_iters']), int(cfg['nb'])
     self.lanes, self.stream = lanes_per_col, stream
-    bb0, bn0 = _rows(cfg['b_basin0'], n, nz), _rows(cfg['b_north0'], n, nz)
-    kap = np.broadcast_to(np.asarray(cfg['kappa'], dtype=np.float64), (n, nz))
-    kapeff = np.broadcast_to(np.asarray(cfg['kappaeff'], dtype=np.float64), (n, nz))
+    bb0, bn0 = rd('b_basin0'), rd('b_north0')
+    kap, kapeff = rd('kappa'), rd('kappaeff')
     # Column(kappa=kappaeff, bbot=b[0]) (:159-171); coefficient set 0 = kappa, 1 = kappaeff
     self.cols = ColumnBatch(
-        z, np.concatenate([kap, kap]),
-        np.concatenate([_rows(cfg['A_basin'], n, nz), _rows(cfg['A_north'], n, nz)]),
-        np.concatenate([bb0, bn0]),
-        bs=np.concatenate([_vec(cfg['bs'], n), _vec(cfg['bs_north'], n)]),
+        z, np.concatenate([kap, kap]), np.concatenate([rd('A_basin'), rd('A_north')]),
+        np.concatenate([bb0, bn0]), bs=np.concatenate([rd('bs'), rd('bs_north')]),
         bbot=np.concatenate([bb0[:, 0], bn0[:, 0]]), do_conv=True,
         kappa_alt=np.concatenate([kapeff, kapeff]), stream=stream)
     self.cols.set_ksel(np.ones(2 * n, dtype=np.int32))
     self.tw = ThermwindBatch(z, n, f=cfg['f'], nb=self.nb, stream=stream, z_dev=self.cols.z)
-    self.so = PsiSOBatch(z, y, n, tau=cfg['tau'], KGM=cfg['KGM'], f=cfg['f'], L=cfg['L'],
+    self.so = PsiSOBatch(z, y, n, tau=rd('tau'), KGM=rd('KGM'), f=cfg['f'], L=cfg['L'],
                          stream=stream, z_dev=self.cols.z)
-    bs0 = cfg['bs_SO0']
-    self.ml = SOMLBatch(y, nz, _rows(bs0, n, ny) if np.ndim(bs0) == 1 else bs0,
-                        surflux=cfg['surflux'], rest_mask=cfg['rest_mask'],
-                        b_rest=cfg['b_rest'], Ks=cfg['Ks'], h=cfg['h'], L=cfg['L'],
+    self.ml = SOMLBatch(y, nz, rd('bs_SO0'), surflux=rd('surflux'), rest_mask=rd('rest_mask'),
+                        b_rest=rd('b_rest'), Ks=cfg['Ks'], h=cfg['h'], L=cfg['L'],
                         v_pist=cfg['v_pist'], stream=stream)
     self.wA = DeviceArray.zeros((2 * n, nz), stream=stream)
-    self._off = n * nz * 8
-    self._bc = pm_jn2018_bc()
+    self.b_basin, self.b_north = self.cols.b.view(0, n), self.cols.b.view(n, n)
+    self.wA_basin, self.wA_north = self.wA.view(0, n), self.wA.view(n, n)
+    self._bc = _lib.pm_jn2018_bc()
     d = self._bc
     d.n, d.nz, d.ny, d.reserved = n, nz, ny, 0
     d.Psi_SO, d.Psi_res_b, d.Psi_res_n = self.so.Psi.ptr, self.tw.psibz1.ptr, self.tw.psibz2.ptr
-    d.b_basin, d.b_north = self.cols.b.ptr, self.cols.b.ptr + self._off
+    d.b_basin, d.b_north = self.b_basin.ptr, self.b_north.ptr
     d.bs_SO, d.bbot, d.ksel = self.ml.bs.ptr, self.cols.bbot.ptr, self.cols.ksel.ptr
-    self._C = C
     self.ii = 0
     self._graph = None
     self._use_graph = use_graph
@@ -449,26 +559,14 @@ class JN2018Ensemble(object):
     self._one_update_launch = bool(cfg.get('one_update_launch', True)) and nz <= 256
     self.diag_iters = (cfg.get('Diag_iters', 10 * self.M) if diag_iters is None
                        else diag_iters)
-    self.diag = None
-    if comm is not None or keep_history:
-      self.diag = DiagnosticGather(comm, n, n if n_total is None else n_total,
-                                   [(k, nz) for k in ('b_basin', 'b_north', 'Psi', 'Psi_SO')],
-                                   stream=stream, keep_history=keep_history, mode=gather,
-                                   overlap=gather_overlap)
-
-  def gather_diagnostics(self, step=None):
-    self.diag.gather(dict(b_basin=self.cols.b.ptr, b_north=self.cols.b.ptr + self._off,
-                          Psi=self.tw.Psi, Psi_SO=self.so.Psi),
-                     step=self.ii if step is None else step)
+    self._init_gather(comm, n_total, keep_history, gather, gather_overlap)
 
   def _after_update(self):
     if self.recorder is not None:
       self.recorder.maybe_record(self.ii)
-    if self.diag is not None and self.diag.due(self.ii, self.diag_iters):
-      self.gather_diagnostics(self.ii)
+    self._gather_if_due(self.ii)
 
   def _update(self):
-    b_basin, b_north = self.cols.b.ptr, self.cols.b.ptr + self._off
     # psib / bgrid go to HBM only in the updates a diagnostics recorder samples right after (every
     # Diag_iters steps, run_JansenNadeau_2018.py:218-226); all the other updates sum only the
     # classes Psibz reads (thermwind.hip.h)
@@ -476,26 +574,22 @@ class JN2018Ensemble(object):
     store = rec is not None and self.ii % rec.Diag_iters == 0
     if self._one_update_launch:
       # PsiSO.solve + AMOC.solve / Psibz of a member by one wave, ONE launch (pm_so_tw_update)
-      ds = self.so.descriptor(b_basin, self.ml.bs)
-      dw = self.tw.descriptor(b_basin, b_north, Psi_SO=self.so.Psi, wA1=self.wA.ptr,
-                              wA2=self.wA.ptr + self._off, store_psib=store)
+      ds = self.so.descriptor(self.b_basin, self.ml.bs)
+      dw = self.tw.descriptor(self.b_basin, self.b_north, Psi_SO=self.so.Psi, wA1=self.wA_basin,
+                              wA2=self.wA_north, store_psib=store)
       with launch_span(self.timer, "k_so_tw_update", self.stream):
-        _lib.check(_lib.lib.pm_so_tw_update(self._C.byref(ds), self._C.byref(dw), _TW_ALL,
-                                            _sh(self.stream)))
+        check(lib.pm_so_tw_update(C.byref(ds), C.byref(dw), _TW_ALL, _sh(self.stream)))
       return
     with launch_span(self.timer, "k_psi_so", self.stream):
-      self.so.update(b_basin, self.ml.bs)
+      self.so.update(self.b_basin, self.ml.bs)
     with launch_span(self.timer, "k_thermwind", self.stream):
-      self.tw.update(b_basin, b_north, ops=_TW_ALL, store_psib=store,
-                     Psi_SO=self.so.Psi, wA1=self.wA.ptr,
-                     wA2=self.wA.ptr + self._off)
+      self.tw.update(self.b_basin, self.b_north, ops=_TW_ALL, store_psib=store,
+                     Psi_SO=self.so.Psi, wA1=self.wA_basin, wA2=self.wA_north)
 
   def _step(self):
-    from ._lib import check, lib
-    from .device import _sh
-    check(lib.pm_jn2018_bc_switch(self._C.byref(self._bc), _sh(self.stream)))
+    check(lib.pm_jn2018_bc_switch(C.byref(self._bc), _sh(self.stream)))
     self.cols.steps(self.wA, self.dt, 1, lanes_per_col=self.lanes)
-    self.ml.step(self.cols.b.ptr, self.so.Psi, self.dt)
+    self.ml.step(self.b_basin, self.so.Psi, self.dt)
 
   def _block(self):
     self._update()
@@ -503,17 +597,14 @@ class JN2018Ensemble(object):
       self._step()
 
   def _fused_steps(self, nsteps):
-    from ._lib import check, lib
-    from .device import _sh
     d = self._jn_descriptor()
     with launch_span(self.timer, "k_jn2018_steps", self.stream):
-      check(lib.pm_jn2018_steps(self._C.byref(d), self.dt, int(nsteps), _sh(self.stream)))
+      check(lib.pm_jn2018_steps(C.byref(d), self.dt, int(nsteps), _sh(self.stream)))
 
   def _div3(self):
     """PM_JN_DIV3_PROVEN: the columns' static denominators (ColumnBatch.div3_proven) and the
     mixed layer's h, L and y[1] - y[0] admit the 3-instruction exact quotient."""
     if not hasattr(self, "_div3_ok"):
-      from .columns import div3_proven, device_reciprocals_exact, _HINT_DIV3_OFF
       t = self.ml
       den = np.array([t.h, t.L, t.y_host[1] - t.y_host[0]], dtype=np.float64)
       a = np.abs(den)
@@ -524,8 +615,7 @@ class JN2018Ensemble(object):
     return self._div3_ok
 
   def _jn_descriptor(self):
-    from ._lib import pm_jn2018, pm_so_ml
-    d = pm_jn2018()
+    d = _lib.pm_jn2018()
     d.n = self.n
     d.hints = _lib.PM_JN_UNIFORM_AREA if self.cols.uniform_area else 0
     if self.arith == "contracted":
@@ -539,7 +629,7 @@ class JN2018Ensemble(object):
     d.cols = self.cols.descriptor()
     d.wA, d.Psi_SO = self.wA.ptr, self.so.Psi.ptr
     d.Psi_res_b, d.Psi_res_n = self.tw.psibz1.ptr, self.tw.psibz2.ptr
-    ml, t = pm_so_ml(), self.ml
+    ml, t = _lib.pm_so_ml(), self.ml
     ml.n, ml.nz, ml.ny, ml.reserved = t.n, t.nz, t.ny, 0
     ml.y, ml.bs, ml.Psi_s = t.y.ptr, t.bs.ptr, t.Psi_s.ptr
     ml.b_basin, ml.Psi_b = None, None
@@ -556,10 +646,7 @@ class JN2018Ensemble(object):
   def _run_fused(self, nsteps):
     """The loop through pm_jn2018_run: one launch per stretch that ends where the script samples
     its diagnostics (right after a MOC update) or at the end of the run."""
-    from ._lib import check, lib
-    from .device import _sh
     M, remaining = self.M, int(nsteps)
-    b_basin, b_north = self.cols.b.ptr, self.cols.b.ptr + self._off
     while remaining > 0:
       ii = self.ii
       sch = _lib.pm_run_schedule()
@@ -580,14 +667,14 @@ class JN2018Ensemble(object):
       sch.n_updates, sch.n_last = len(blocks), (blocks[-1] if blocks else 0)
       d = _lib.pm_jn2018_loop()
       d.jn = self._jn_descriptor()
-      d.so = self.so.descriptor(b_basin, self.ml.bs)
-      d.tw = self.tw.descriptor(b_basin, b_north, Psi_SO=self.so.Psi, wA1=self.wA.ptr,
-                                wA2=self.wA.ptr + self._off,
+      d.so = self.so.descriptor(self.b_basin, self.ml.bs)
+      d.tw = self.tw.descriptor(self.b_basin, self.b_north, Psi_SO=self.so.Psi,
+                                wA1=self.wA_basin, wA2=self.wA_north,
                                 store_psib=self.recorder is not None)
       d.dt, d.sched = self.dt, sch
       check(lib.pm_memset(self.ml.status.ptr, 0, self.ml.status.nbytes, _sh(self.stream)))
       with launch_span(self.timer, "k_jn2018_run", self.stream):
-        check(lib.pm_jn2018_run(self._C.byref(d), _sh(self.stream)))
+        check(lib.pm_jn2018_run(C.byref(d), _sh(self.stream)))
       remaining -= pos - ii
       self.ii = pos
       if stopped:
@@ -595,7 +682,6 @@ class JN2018Ensemble(object):
         self._after_update()
 
   def run(self, nsteps):
-    from .device import Graph
     if self._fused_run:
       return self._run_fused(nsteps)
     remaining = int(nsteps)
@@ -636,19 +722,18 @@ class JN2018Ensemble(object):
       self._after_update()
       self._updated_at = self.ii
 
+  at_restart_point = moc_update
+
+  def drift_fields(self):
+    return CoupledEnsemble.drift_fields(self) + [("bs_SO", self.ml.bs, self.ny, self.ny)]
+
   def state(self):
-    b = self.cols.get_b()
-    return dict(b_basin=b[:self.n], b_north=b[self.n:], bs_SO=self.ml.bs.download(stream=self.stream),
-                Psi=self.tw.Psi.download(stream=self.stream), Psi_SO=self.so.Psi.download(stream=self.stream),
-                Psi_iso_b=self.tw.psibz1.download(stream=self.stream), Psi_iso_n=self.tw.psibz2.download(stream=self.stream),
-                Psi_s=self.ml.Psi_s.download(stream=self.stream))
-
-  def nonfinite_members(self):
-    nf = self.cols.get_nonfinite()
-    return np.nonzero(nf[:self.n] | nf[self.n:])[0]
+    return self._download(b_basin=self.b_basin, b_north=self.b_north, bs_SO=self.ml.bs,
+                          Psi=self.tw.Psi, Psi_SO=self.so.Psi, Psi_iso_b=self.tw.psibz1,
+                          Psi_iso_n=self.tw.psibz2, Psi_s=self.ml.Psi_s)
 
 
-class TwoBasinEnsemble(object):
+class TwoBasinEnsemble(CoupledEnsemble):
   """twobasin_NadeauJansen.py: Atlantic, northern-sinking and Pacific columns; AMOC
   (Atl vs north) and zonal (Atl vs Pac) thermal-wind overturnings mapped to isopycnal space;
   one Southern-Ocean overturning per basin sector.  Columns are stored Atl rows [0,n),
@@ -666,13 +751,16 @@ class TwoBasinEnsemble(object):
   (:124-133): the three columns' b and the four overturnings.  `arith="contracted"`: the columns
   step in the opt-in tolerance mode."""
 
+  NGROUPS = 3
   FIELDS = ("b_Atl", "b_north", "b_Pac", "Psi_AMOC", "Psi_ZOC", "Psi_SO_Atl", "Psi_SO_Pac")
+
+  @classmethod
+  def members(cls, cfg):
+    return np.size(cfg['tau']) if np.ndim(cfg['tau']) else 1
 
   def __init__(self, cfg, stream=None, lanes_per_col=0, comm=None, n_total=None,
                diag_iters=None, keep_history=False, arith="exact", overlap_updates=False,
                gather="all", gather_overlap=True, use_graph=True):
-    if arith not in ("exact", "contracted"):
-      raise ValueError("arith must be 'exact' or 'contracted'")
     # Measured at 2048 members (profiles/r05/probe_c6_modes.py, us per interval of 24 steps):
     #   the two update pairs one after the other on ONE stream, the forcing formed by the column
     #   kernel (PM_OP_WA_TWOBASIN): 58.2 -- the default;  ... with pm_twobasin_forcing: 63.8;
@@ -681,13 +769,14 @@ class TwoBasinEnsemble(object):
     #   with overlap_updates, off while a LaunchTimer is attached).  With the round-5 thermal wind
     #   a pair is 17 us: the events cost more than the overlap gives.  (Both pairs as the halves
     #   of ONE launch: 33 us against 2 x 17 -- not kept.)
+    self.arith = self._check_arith(arith)
     self._use_graph, self._graph = bool(use_graph), None
     z, y = cfg['z'], cfg['y']
     nz, ny = z.size, y.size
-    n = np.size(cfg['tau']) if np.ndim(cfg['tau']) else 1
+    n = self.members(cfg)
     self.n, self.nz, self.ny = n, nz, ny
     self.dt, self.M, self.nb = float(cfg['dt']), int(cfg['MOC_up_iters']), int(cfg['nb'])
-    self.lanes, self.stream, self.arith = lanes_per_col, stream, arith
+    self.lanes, self.stream = lanes_per_col, stream
     self.timer = None  # optional device.LaunchTimer
     kap = _rows(cfg['kappa'], n, nz)
     rows = lambda v: _rows(v, n, nz)  # noqa: E731
@@ -715,39 +804,30 @@ class TwoBasinEnsemble(object):
     self.bs_SO = DeviceArray.from_host(_rows(cfg['bs_SO'], n, ny) if np.ndim(cfg['bs_SO']) == 1
                                        else cfg['bs_SO'], stream=stream)
     self.wA = DeviceArray.zeros((3 * n, nz), stream=stream)
-    self._off = n * nz * 8
+    b, w = self.cols.b, self.wA
+    self.b_Atl, self.b_north, self.b_Pac = b.view(0, n), b.view(n, n), b.view(2 * n, n)
+    self.wA_Atl, self.wA_north, self.wA_Pac = w.view(0, n), w.view(n, n), w.view(2 * n, n)
     self.ii = 0
     self.diag_iters = (cfg.get('plot_iters', cfg.get('Diag_iters', 10 * self.M))
                        if diag_iters is None else diag_iters)
-    self.diag = None
-    if comm is not None or keep_history:
-      self.diag = DiagnosticGather(comm, n, n if n_total is None else n_total,
-                                   [(k, nz) for k in self.FIELDS], stream=stream,
-                                   keep_history=keep_history, mode=gather,
-                                   overlap=gather_overlap)
+    self._init_gather(comm, n_total, keep_history, gather, gather_overlap)
     self._pairs = nz <= 256   # pm_so_tw_update covers the shape
     self._overlap = bool(overlap_updates)
     if self._overlap:
-      from .device import Event, Stream
-      self._side = Stream()
-      self._ev_fork, self._ev_join = Event(), Event()
+      self._side, self._ev_fork, self._ev_join = Stream(), Event(), Event()
     # initial diagnostics (:58-79): AMOC against b2 = 0.01*b_Atl, the rest on the initial columns
     b2 = DeviceArray.from_host(rows(cfg['b2_init']), stream=stream)
-    self._update(b_north=b2.ptr)
-    if stream is not None:
-      stream.sync()  # b2 is released on return
-    else:
-      _lib.check(_lib.lib.pm_stream_sync(None))
+    self._update(b_north=b2)
+    check(lib.pm_stream_sync(_sh(stream)))  # b2 is released on return
 
-  def _solve_pair(self, so, tw, b_so, b1, b2, stream, names):
+  def _solve_pair(self, so, tw, b_so, b1, b2, stream):
     """{Psi_SO.solve on b_so, thermal wind of (b1, b2)} on `stream`: one launch when the shape
     allows, else two."""
-    import ctypes as C
     if self._pairs:
       ds = so.descriptor(b_so, self.bs_SO)
       dw = tw.descriptor(b1, b2, store_psib=False)
       with launch_span(self.timer, "k_so_tw_update", stream):
-        _lib.check(_lib.lib.pm_so_tw_update(C.byref(ds), C.byref(dw), _TW_ALL, _sh(stream)))
+        check(lib.pm_so_tw_update(C.byref(ds), C.byref(dw), _TW_ALL, _sh(stream)))
       return
     keep_so, keep_tw = so.stream, tw.stream
     so.stream = tw.stream = stream
@@ -760,20 +840,15 @@ class TwoBasinEnsemble(object):
       so.stream, tw.stream = keep_so, keep_tw
 
   def _update(self, b_north=None):
-    from ._lib import check, lib
-    bA = self.cols.b.ptr
-    bN = self.cols.b.ptr + self._off if b_north is None else b_north
-    bP = self.cols.b.ptr + 2 * self._off
+    bA, bP = self.b_Atl, self.b_Pac
+    bN = self.b_north if b_north is None else b_north
+    atl = lambda st: self._solve_pair(self.so_atl, self.amoc, bA, bA, bN, st)  # noqa: E731
+    pac = lambda st: self._solve_pair(self.so_pac, self.zoc, bP, bA, bP, st)   # noqa: E731
     if self._overlap:
-      self._ev_fork.record(self.stream)     # the columns' steps before this update
-      self._side.wait(self._ev_fork)
-      self._solve_pair(self.so_pac, self.zoc, bP, bA, bP, self._side, "pac")
-      self._ev_join.record(self._side)
-      self._solve_pair(self.so_atl, self.amoc, bA, bA, bN, self.stream, "atl")
-      check(lib.pm_stream_wait_event(_sh(self.stream), self._ev_join.handle))
+      self._side_by_side(pac, atl)
     else:
-      self._solve_pair(self.so_atl, self.amoc, bA, bA, bN, self.stream, "atl")
-      self._solve_pair(self.so_pac, self.zoc, bP, bA, bP, self.stream, "pac")
+      atl(self.stream)
+      pac(self.stream)
     self._wA_fresh = False
     if not self._forcing_in_k1:
       self._form_forcing()
@@ -781,12 +856,10 @@ class TwoBasinEnsemble(object):
   def _form_forcing(self):
     """wA of the three columns as an array (:103-105; launches of 1-2 steps, and
     `_forcing_in_k1 = False`): pm_twobasin_forcing."""
-    from ._lib import check, lib
-    w = self.wA.ptr
     check(lib.pm_twobasin_forcing(self.n, self.nz, self.amoc.psibz1.ptr, self.zoc.psibz1.ptr,
                                   self.so_atl.Psi.ptr, self.amoc.psibz2.ptr,
-                                  self.zoc.psibz2.ptr, self.so_pac.Psi.ptr, w, w + self._off,
-                                  w + 2 * self._off, _sh(self.stream)))
+                                  self.zoc.psibz2.ptr, self.so_pac.Psi.ptr, self.wA_Atl.ptr,
+                                  self.wA_north.ptr, self.wA_Pac.ptr, _sh(self.stream)))
     self._wA_fresh = True
 
   def _steps(self, n):
@@ -803,12 +876,10 @@ class TwoBasinEnsemble(object):
   def run(self, nsteps):
     remaining = int(nsteps)
     while remaining > 0:
-      nxt = self.ii if self.ii % self.M == 0 else (self.ii // self.M + 1) * self.M
-      n = min(nxt - self.ii + 1, remaining)
+      n = self._interval(remaining)
       if (self._use_graph and self.timer is None and self._overlap and n == self.M and
           self.ii % self.M == 1 and self.M >= 3):
         # a full interval: M steps, then the update they end on
-        from .device import Graph
         if self._graph is None:
           with Graph.capture(self.stream) as cap:
             self._steps(n)
@@ -817,8 +888,7 @@ class TwoBasinEnsemble(object):
         self._graph.launch(self.stream)
         self.ii += n
         remaining -= n
-        if self.diag is not None and self.diag.due(self.ii - 1, self.diag_iters):
-          self.gather_diagnostics(self.ii - 1)
+        self._gather_if_due(self.ii - 1)
         continue
       with launch_span(self.timer, "k_column_steps" if n >= 3 else "k_column_steps_short",
                        self.stream):
@@ -827,23 +897,13 @@ class TwoBasinEnsemble(object):
       remaining -= n
       if (self.ii - 1) % self.M == 0:
         self._update()
-        if self.diag is not None and self.diag.due(self.ii - 1, self.diag_iters):
-          self.gather_diagnostics(self.ii - 1)
+        self._gather_if_due(self.ii - 1)
 
-  def gather_diagnostics(self, step=None):
-    """Gather the seven fields the script samples every plot_iters steps (:124-133)."""
-    b = self.cols.b.ptr
-    self.diag.gather(dict(b_Atl=b, b_north=b + self._off, b_Pac=b + 2 * self._off,
-                          Psi_AMOC=self.amoc.Psi, Psi_ZOC=self.zoc.Psi,
-                          Psi_SO_Atl=self.so_atl.Psi, Psi_SO_Pac=self.so_pac.Psi),
-                     step=self.ii if step is None else step)
+  def fields(self):
+    """The seven fields the script samples every plot_iters steps (:124-133)."""
+    return dict(b_Atl=self.b_Atl, b_north=self.b_north, b_Pac=self.b_Pac,
+                Psi_AMOC=self.amoc.Psi, Psi_ZOC=self.zoc.Psi, Psi_SO_Atl=self.so_atl.Psi,
+                Psi_SO_Pac=self.so_pac.Psi)
 
   def state(self):
-    b, n = self.cols.get_b(), self.n
-    return dict(b_Atl=b[:n], b_north=b[n:2 * n], b_Pac=b[2 * n:], Psi_AMOC=self.amoc.Psi.download(stream=self.stream),
-                Psi_ZOC=self.zoc.Psi.download(stream=self.stream), Psi_SO_Atl=self.so_atl.Psi.download(stream=self.stream),
-                Psi_SO_Pac=self.so_pac.Psi.download(stream=self.stream))
-
-  def nonfinite_members(self):
-    nf, n = self.cols.get_nonfinite(), self.n
-    return np.nonzero(nf[:n] | nf[n:2 * n] | nf[2 * n:])[0]
+    return self._download(**self.fields())

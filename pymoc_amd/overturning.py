@@ -109,7 +109,8 @@ class OverturningSections(object):
         raise ValueError("inputs hold %d rows, n is %d" % (c, self.n))
     for name, _, shape in shapes:
       dev, off, stride = self.inputs[name]
-      if self.n > 0 and (off + (self.n - 1) * stride + int(np.prod(shape))) * 8 > dev.nbytes:
+      last = off + (self.n - 1) * stride + int(np.prod(shape))
+      if self.n > 0 and last * dev.dtype.itemsize > dev.nbytes:
         raise ValueError("%s: member rows run past the end of the device array" % name)
     self._c = [DeviceArray.from_host(self.rows[k], stream=stream) for k in ("c1", "c2", "c3")]
     m = max(self.n, 1)
@@ -209,11 +210,10 @@ class OverturningSections(object):
     if self._sources is not None:
       ens = self._sources
       stream = None  # the private solvers launch on the ensemble's stream, and so does the kernel
-      b_basin, b_north = ens.cols.b.ptr, ens.cols.b.ptr + ens.n * ens.nz * 8
       self.channel.grid()
       self.north.grid()
-      self.so.update(b_basin, ens.ml.bs)
-      self.tw.update(b_basin, b_north, store_psib=True)
+      self.so.update(ens.b_basin, ens.ml.bs)
+      self.tw.update(ens.b_basin, ens.b_north, store_psib=True)
     return self.launch(stream)
 
   def launch(self, stream=None):

@@ -92,7 +92,7 @@ class SectionBatch(object):
       dev, off, stride, scalar = p
       if isinstance(dev, DeviceArray) and self.n > 0:
         last = off + (self.n - 1) * stride + (1 if scalar else length)
-        if last * 8 > dev.nbytes:
+        if last * dev.dtype.itemsize > dev.nbytes:
           raise ValueError("%s: member rows run past the end of the device array" % name)
     if self.fixups and self.flags:
       raise ValueError("fix-ups need array profiles")

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .device import DeviceArray, Event, PinnedArray, download_async, rows_pack, _sh
-from .ensembles import JN2018Ensemble, TwoColEnsemble, _rows
+from .ensembles import CoupledEnsemble
 
 YEAR = 360 * 86400.  # the scripts' year (run_JansenNadeau_2018.py:39)
 
@@ -32,70 +32,31 @@ CONVERGED = _lib.PM_STEADY_CONVERGED
 NONFINITE = _lib.PM_STEADY_NONFINITE
 MAXSTEPS = _lib.PM_STEADY_MAXSTEPS
 
-# how each constructor reads a per-member key: ("vec",) = _vec(v, n); ("rows", axis) =
-# _rows(v, n, axis.size); ("2d",) = a 2-D array is per member, anything else is shared (np.broadcast_to
-# of the JN2018 kappa profiles, SOMLBatch's surflux / rest_mask / b_rest, a wind-stress profile)
-_KEYS = {
-    "jn2018": dict(kappa=("2d",), kappaeff=("2d",), A_basin=("rows", "z"), A_north=("rows", "z"),
-                   bs=("vec",), bs_north=("vec",), tau=("vec",), KGM=("vec",),
-                   surflux=("2d",), rest_mask=("2d",), b_rest=("2d",),
-                   b_basin0=("rows", "z"), b_north0=("rows", "z"), bs_SO0=("rows", "y")),
-    "twocol": dict(kappa=("rows", "z"), A_basin=("rows", "z"), A_north=("rows", "z"),
-                   bs=("vec",), bs_north=("vec",), bbot=("vec",), tau=("vec",), KGM=("vec",),
-                   bs_SO=("rows", "y"), b_basin0=("rows", "z"), b_north0=("rows", "z")),
-}
-_S0 = {"jn2018": 0, "twocol": 1}
 
-
-def _kind(cls):
-  if cls is JN2018Ensemble:
-    return "jn2018"
-  if cls is TwoColEnsemble:
-    return "twocol"
-  raise ValueError("run_to_steady supports JN2018Ensemble and TwoColEnsemble, not %r"
-                   % getattr(cls, "__name__", cls))
-
-
-def _members(cfg):
-  return np.atleast_2d(cfg["b_basin0"]).shape[0]
+def _restartable(cls):
+  """`cls` if it states how its cfg is read per member and where it can be restarted
+  (CoupledEnsemble.MEMBER_KEYS, RESTART_PHASE)."""
+  if not (isinstance(cls, type) and issubclass(cls, CoupledEnsemble) and cls.MEMBER_KEYS):
+    raise ValueError("run_to_steady supports JN2018Ensemble and TwoColEnsemble, not %r"
+                     % getattr(cls, "__name__", cls))
+  return cls
 
 
 def restrict_cfg(cls, cfg, keep):
   """`cfg` restricted to members `keep` (indices into its current members), by the rule the
-  constructor of `cls` reads each key with: a per-member key is expanded to explicit [n, ...] at
-  the current n, then indexed -- so a 1-D per-member array never comes back as a length-nz vector
-  that `_rows` would read as a profile.  Shared keys are passed on unchanged."""
-  kind = _kind(cls)
-  n = _members(cfg)
-  keep = np.asarray(keep, dtype=np.int64)
-  out = dict(cfg)
-  for key, rule in _KEYS[kind].items():
-    if key not in cfg:
-      continue
-    a = np.asarray(cfg[key], dtype=np.float64)
-    if rule[0] == "vec":
-      if a.ndim >= 1:
-        out[key] = a[keep]
-    elif rule[0] == "2d":
-      if a.ndim == 2:
-        out[key] = a[keep]
-    else:
-      nlev = np.asarray(cfg[rule[1]]).size
-      if a.ndim == 2 or (a.ndim == 1 and a.shape[0] == n and n != nlev):
-        out[key] = _rows(a, n, nlev)[keep]
-  return out
+  constructor of `cls` reads each key with (CoupledEnsemble.restrict)."""
+  return _restartable(cls).restrict(cfg, keep)
 
 
 def check_schedule(cls, moc_up_iters, check_every, max_steps):
   """(s0, [check steps]): the first snapshot at s0, then a check every `check_every` steps; the
   last check falls on the last restartable step <= max_steps (it finalizes)."""
-  kind = _kind(cls)
+  s0 = _restartable(cls).RESTART_PHASE
   M, E, S = int(moc_up_iters), int(check_every), int(max_steps)
   if M < 1:
     raise ValueError("MOC_up_iters must be >= 1")
   if E < 1 or E % M:
     raise ValueError("check_every=%d is not a positive multiple of MOC_up_iters=%d" % (E, M))
-  s0 = _S0[kind]
   last = s0 + ((S - s0) // M) * M if S >= s0 else s0
   if last <= s0:
     raise ValueError("max_steps=%d leaves no check after the first snapshot at step %d"
@@ -104,7 +65,7 @@ def check_schedule(cls, moc_up_iters, check_every, max_steps):
 
 
 def _validate(cls, cfg, kw, check_every):
-  kind = _kind(cls)
+  _restartable(cls)
   if kw.get("arith", "exact") != "exact":
     raise ValueError("run_to_steady needs arith='exact' (its results are bit-identical to a "
                      "plain run)")
@@ -116,7 +77,7 @@ def _validate(cls, cfg, kw, check_every):
   M = int(cfg["MOC_up_iters"])
   if check_every is None:
     check_every = cfg.get("Diag_iters") or 10 * M
-  return kind, M, int(check_every)
+  return M, int(check_every)
 
 
 class SteadyResult(object):
@@ -147,14 +108,14 @@ class _Run(object):
   """The device side of one run_to_steady: snapshot, capture and per-member arrays, the current
   ensemble and its rows' original member numbers."""
 
-  def __init__(self, cls, kind, cfg, kw, tol, consecutive):
-    self.cls, self.kind, self.cfg, self.kw = cls, kind, cfg, kw
+  def __init__(self, cls, cfg, kw, tol, consecutive):
+    self.cfg, self.kw = cfg, kw
     self.stream = kw.get("stream")
     self.ens = cls(cfg, **kw)
     self.n0 = self.rows = self.ens.n
     self.consecutive = consecutive
-    d = self._fields()
-    self.drift_names = [f[0] for f in d[:self._ndrift()]]
+    d = self.ens.capture_fields()
+    self.drift_names = [f[0] for f in self.ens.drift_fields()]
     self.capture_names = [f[0] for f in d]
     self.lens = {f[0]: f[3] for f in d}
     st = self.stream
@@ -172,33 +133,16 @@ class _Run(object):
     self.pinned = PinnedArray((2,), np.int32)
     self.events = [Event(), Event()]
 
-  def _ndrift(self):
-    return 3 if self.kind == "jn2018" else 2
-
-  def _fields(self):
-    """(name, device address, row stride, len) of the drift fields, then the other captures."""
-    e = self.ens
-    nz = e.nz
-    if self.kind == "jn2018":
-      return [("b_basin", e.cols.b.ptr, nz, nz), ("b_north", e.cols.b.ptr + e._off, nz, nz),
-              ("bs_SO", e.ml.bs.ptr, e.ny, e.ny), ("Psi", e.tw.Psi.ptr, nz, nz),
-              ("Psi_SO", e.so.Psi.ptr, nz, nz)]
-    f = [("b_basin", e._b_basin, nz, nz), ("b_north", e._b_north, nz, nz),
-         ("Psi", e.tw.Psi.ptr, nz, nz)]
-    if e.so is not None:
-      f.append(("Psi_SO", e.so.Psi.ptr, nz, nz))
-    return f
-
   def snapshot(self):
     """The first snapshot: every drift field's rows, identity selection."""
-    rows_pack([(src, self.snap[k].ptr, ln, stride) for k, src, stride, ln in
-               self._fields()[:self._ndrift()]], self.rows, None, self.stream)
+    rows_pack([(src.ptr, self.snap[k].ptr, ln, stride) for k, src, stride, ln in
+               self.ens.drift_fields()], self.rows, None, self.stream)
 
   def check(self, step, interval, finalize, slot):
     c = _lib.pm_steady_check()
     c.n, c.n0 = self.rows, self.n0
-    fields = self._fields()
-    c.ndrift, c.ncapture = self._ndrift(), len(fields)
+    fields = self.ens.capture_fields()  # the drift fields first
+    c.ndrift, c.ncapture = len(self.drift_names), len(fields)
     c.consecutive, c.finalize, c.step = self.consecutive, int(bool(finalize)), int(step)
     c.scale = YEAR / (interval * self.ens.dt)
     c.orig, c.tol, c.streak, c.status = (self.orig.ptr, self.tol.ptr, self.streak.ptr,
@@ -207,9 +151,9 @@ class _Run(object):
     for i, (k, src, stride, ln) in enumerate(fields):
       if i < c.ndrift:
         c.drift[i].src, c.drift[i].src_stride, c.drift[i].buf, c.drift[i].len = (
-            src, stride, self.snap[k].ptr, ln)
+            src.ptr, stride, self.snap[k].ptr, ln)
       c.capture[i].src, c.capture[i].src_stride, c.capture[i].buf, c.capture[i].len = (
-          src, stride, self.cap[k].ptr, ln)
+          src.ptr, stride, self.cap[k].ptr, ln)
     _lib.check(_lib.lib.pm_steady_check(C.byref(c), _sh(self.stream)))
     download_async(self.n_running.ptr, 4, self.pinned, self.stream, offset=4 * slot)
     self.events[slot].record(self.stream)
@@ -229,16 +173,9 @@ class _Run(object):
     keep = np.nonzero(status[self.orig_h] == RUNNING)[0]
     if keep.size == 0 or keep.size == self.rows:
       return keep.size
-    e, st = self.ens, self.stream
-    b = e.cols.get_b()
-    cfg = restrict_cfg(self.cls, self.cfg, keep)
-    cfg["b_basin0"], cfg["b_north0"] = b[:e.n][keep], b[e.n:2 * e.n][keep]
-    if self.kind == "jn2018":
-      cfg["bs_SO0"] = e.ml.bs.download(stream=st)[keep]
-    new = self.cls(cfg, **self.kw)  # TwoColEnsemble: its constructor's update is the one at s
-    new.ii = e.ii
-    if self.kind == "jn2018":
-      new.moc_update()
+    st = self.stream
+    new = self.ens.subset(keep, self.cfg, self.kw)
+    cfg = type(new).restrict(self.cfg, keep)  # (its state keys are replaced at the next subset)
     sel = DeviceArray.from_host(keep.astype(np.int32), stream=st)
     snap = {k: DeviceArray((keep.size, self.lens[k])) for k in self.drift_names}
     rows_pack([(self.snap[k].ptr, snap[k].ptr, self.lens[k], self.lens[k])
@@ -264,19 +201,19 @@ def run_to_steady(cls, cfg, tol, max_steps, check_every=None, consecutive=1, com
                 is still running (0: never, 1: at every check that retired a member)
 Returns a SteadyResult.  Refused (ValueError): other classes, arith != 'exact', fused_run, comm,
 keep_history, a check_every that is not a multiple of MOC_up_iters."""
-  kind, M, check_every = _validate(cls, cfg, ensemble_kwargs, check_every)
+  M, check_every = _validate(cls, cfg, ensemble_kwargs, check_every)
   s0, checks = check_schedule(cls, M, check_every, max_steps)
   if int(consecutive) < 1:
     raise ValueError("consecutive must be >= 1")
   if not 0. <= float(compact_below) <= 1.:
     raise ValueError("compact_below must lie in [0, 1]")
-  n0 = _members(cfg)
+  n0 = cls.members(cfg)
   tol = np.asarray(tol, dtype=np.float64)
   tol = np.full(n0, tol) if tol.ndim == 0 else tol
   if tol.shape != (n0,) or np.isnan(tol).any():
     raise ValueError("tol must be a scalar or one non-NaN value per member (%d)" % n0)
 
-  r = _Run(cls, kind, cfg, dict(ensemble_kwargs), tol, int(consecutive))
+  r = _Run(cls, cfg, dict(ensemble_kwargs), tol, int(consecutive))
   compactions, member_steps = [], 0
   if s0:
     r.ens.run(s0)  # TwoColEnsemble: step 0 and the update that follows it
@@ -288,8 +225,7 @@ keep_history, a check_every that is not a multiple of MOC_up_iters."""
     nsteps = s - r.ens.ii
     r.ens.run(nsteps)
     member_steps += r.rows * nsteps
-    if kind == "jn2018":
-      r.ens.moc_update()
+    r.ens.at_restart_point()
     slot = j % 2
     r.check(s, s - prev, final, slot)
     prev = s

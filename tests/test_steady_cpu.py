@@ -81,46 +81,32 @@ def _jn_cfg(N, nz=81, rest_mask_2d=False):
   return cfg
 
 
-def _expand(kind, cfg, key, n):
-  """How the constructor reads `key` of `cfg` with n members, as an explicit [n, ...] array."""
-  from pymoc_amd.ensembles import _rows, _vec
-  from pymoc_amd.steady import _KEYS
-  rule = _KEYS[kind][key]
-  v = cfg[key]
-  if rule[0] == "vec":
-    return _vec(v, n)
-  if rule[0] == "2d":
-    a = np.asarray(v, dtype=np.float64)
-    return a if a.ndim == 2 else np.broadcast_to(a, (n,) + a.shape[-1:] if a.ndim else (n,))
-  return _rows(v, n, np.asarray(cfg[rule[1]]).size)
-
-
 @pytest.mark.parametrize("case", ["jn_new_n_is_nz", "jn_rest_mask_2d", "twocol_new_n_is_nz",
                                   "twocol_so"])
 def test_restrict_cfg_reads_like_the_constructor(case):
   from pymoc_amd import JN2018Ensemble, TwoColEnsemble, configs
-  from pymoc_amd.steady import _KEYS, restrict_cfg
+  from pymoc_amd.steady import restrict_cfg
   rng = np.random.default_rng(7)
   if case.startswith("jn"):
-    cls, kind, nz = JN2018Ensemble, "jn2018", 81
+    cls, nz = JN2018Ensemble, 81
     cfg = _jn_cfg(120, nz=nz, rest_mask_2d=case == "jn_rest_mask_2d")
     n = 120
   elif case == "twocol_new_n_is_nz":
-    cls, kind, nz = TwoColEnsemble, "twocol", 100
+    cls, nz = TwoColEnsemble, 100
     cfg = configs.config3(N=130, nz=nz)
     n = 130
   else:
-    cls, kind, nz = TwoColEnsemble, "twocol", 100
+    cls, nz = TwoColEnsemble, 100
     cfg = configs.config4(N=120, nz=nz)
     n = 120
   # the new n equals nz: a 1-D per-member key restricted to length nz would be read as a profile
   keep = np.sort(rng.choice(n, nz if case != "jn_rest_mask_2d" else 17, replace=False))
   out = restrict_cfg(cls, cfg, keep)
-  for key in _KEYS[kind]:
+  for key in cls.MEMBER_KEYS:
     if key not in cfg:
       continue
-    got = np.asarray(_expand(kind, out, key, keep.size), dtype=np.float64)
-    want = np.asarray(_expand(kind, cfg, key, n), dtype=np.float64)
+    got = np.asarray(cls.read(out, key, keep.size), dtype=np.float64)
+    want = np.asarray(cls.read(cfg, key, n), dtype=np.float64)
     if want.shape[:1] == (n,):
       want = want[keep]
     assert np.array_equal(np.broadcast_to(got, want.shape), want), key
@@ -136,10 +122,10 @@ def test_restrict_cfg_reads_like_the_constructor(case):
   sub = np.array([0, 3, 5])
   twice = restrict_cfg(cls, out, sub)
   once = restrict_cfg(cls, cfg, keep[sub])
-  for key in _KEYS[kind]:
+  for key in cls.MEMBER_KEYS:
     if key in cfg:
-      a = _expand(kind, twice, key, 3)
-      b = _expand(kind, once, key, 3)
+      a = cls.read(twice, key, 3)
+      b = cls.read(once, key, 3)
       assert np.array_equal(np.broadcast_to(a, np.shape(b)), b), key
 
 

@@ -291,3 +291,65 @@ def test_jn2018_equilibrium_example_runs(gpu, tmp_path):
   z = np.load(out)
   assert z["status"].shape == (24,) and set(np.unique(z["status"])) <= {1, 2, 3}
   assert z["Psi"].shape == (24, 81)
+
+
+# ---------------------------------------------------------------- the base class's protocol
+
+# The config builders take any nz, so the grids are the smallest ones this suite runs each driver
+# on elsewhere (test_fused_run_gpu.py: config 3 at nz = 65, config 5 at nz = 46 with dt = 30 d;
+# config 4's channel solve at nz = 100): the checks below are about how a cfg is read and where a
+# run restarts, not about kernel shapes nothing else vouches for.
+def _case(name, N):
+  from pymoc_amd import JN2018Ensemble, TwoColEnsemble, configs
+  if name == "config3":
+    return TwoColEnsemble, configs.config3(N=N, nz=65)
+  if name == "config4":
+    return TwoColEnsemble, configs.config4(N=N, nz=100)
+  return JN2018Ensemble, configs.config5(N=N, nz=46, dt_days=30)
+
+
+_CASE_NZ = {"config3": 65, "config4": 100, "config5": 46}
+
+
+@pytest.mark.parametrize("shape", ["n3", "n_is_nz"])
+@pytest.mark.parametrize("name", ["config3", "config4", "config5"])
+def test_constructor_reads_member_keys_like_read(gpu, name, shape):
+  """An ensemble built from a cfg as its builder returns it, and one from a cfg whose MEMBER_KEYS
+  entries are replaced by `cls.read(cfg, key, n)`, are bitwise equal after one MOC interval.  At
+  N == nz a 1-D per-member array and a profile have the same shape: a constructor that read a key
+  by another rule than `read` would diverge there."""
+  N = 3 if shape == "n3" else _CASE_NZ[name]
+  cls, cfg = _case(name, N)
+  assert cls.members(cfg) == N
+  explicit = dict(cfg)
+  for key in cls.MEMBER_KEYS:
+    if key in cfg:
+      explicit[key] = cls.read(cfg, key, N)
+      assert explicit[key].shape[0] == N
+  a, b = cls(cfg), cls(explicit)
+  for e in (a, b):
+    e.run(cls.RESTART_PHASE + e.M)
+  sa, sb = a.state(), b.state()
+  assert list(sa) == list(sb)
+  for f in sa:
+    assert _same(sa[f], sb[f]), f
+  assert np.array_equal(a.nonfinite_members(), b.nonfinite_members())
+
+
+@pytest.mark.parametrize("name", ["config3", "config4", "config5"])
+def test_subset_continues_bit_identically(gpu, name):
+  """`subset` at a restart point: members 0, 2, 4 on their own continue bitwise as they do inside
+  the full ensemble, in every field of state()."""
+  cls, cfg = _case(name, 5)
+  keep = [0, 2, 4]
+  full = cls(cfg)
+  full.run(cls.RESTART_PHASE + 2 * full.M)
+  full.at_restart_point()
+  sub = full.subset(keep, cfg, {})
+  assert type(sub) is cls and sub.n == 3 and sub.ii == full.ii
+  for e in (full, sub):
+    e.run(2 * e.M)
+  sf, ss = full.state(), sub.state()
+  assert list(sf) == list(ss)
+  for f in sf:
+    assert _same(sf[f][keep], ss[f]), f
