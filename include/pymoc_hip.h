@@ -798,6 +798,110 @@ typedef struct pm_overturning {
 
 int pm_overturning_sections(const pm_overturning *d, pm_stream_t stream);
 
+/* ------------------------------------------------------- two-basin overturning sections
+ * What examples/twobasin_NadeauJansen.py builds after its loop (:157-262), for every member of an
+ * ensemble: eight overturning fields and three buoyancy sections on the section [nrows][nz] of
+ * channel (ny rows), basin (n_basin), northern transition (n_trans) and northern sinking region
+ * (n_north), nrows = ny + n_basin + n_trans + n_north (the script: 51 + 60 + 20 + 20).
+ *
+ * pm_twobasin_profiles (:161, :192-193) -- the two derived rows the section interpolators need:
+ *   b_basin = (A_Atl*b_Atl + A_Pac*b_Pac)/(A_Atl + A_Pac)          A_* one double per member
+ *   bn      = b_north with bn[0] = b_basin[0]
+ *
+ * pm_twobasin_overturning_sections (:166-168, :203-262).  Per member, once:
+ *   b_basin as above;  sum = Psi_SO_Atl + Psi_SO_Pac;  iA = np.interp(b_basin, b_Atl, Psi_SO_Atl),
+ *   iP = np.interp(b_basin, b_Pac, Psi_SO_Pac), PsiSO = iA + iP                        (:166-167)
+ *   Ab = np.interp(b_basin, bgrid_AMOC, psib_AMOC)                                     (:168)
+ *   Zb = np.interp(b_basin, bgrid_ZOC, psib_ZOC)                                       (:236, :239)
+ * then with x = bnew[iy] (the row of the assembled section), c1..c3 the row coefficients:
+ *   row 0            zero in all eight fields (the script's loop starts at 1)
+ *   channel, >= 1    Z = Z_ATL = Z_PAC = np.interp(x, b_basin, sum)                    (:218-220)
+ *                    B = B_ATL = B_PAC = PsiSO[k] where b_basin[k] < bs_SO[iy], else 0 (:221-225)
+ *                    ATL = PAC = np.interp(x, b_basin, PsiSO)                          (:222, :224)
+ *   basin            Z     = (c1*Psi_AMOC + c2*sum)/lbasin                             (:228)
+ *                    Z_ATL = (c1*Psi_AMOC + c2*(Psi_SO_Atl - Psi_ZOC))/lbasin          (:229)
+ *                    Z_PAC = (c2*(Psi_SO_Pac + Psi_ZOC))/lbasin                        (:230)
+ *                    B     = (c1*Ab + c2*PsiSO)/lbasin                                 (:231-232)
+ *                    ATL   = (c1*psibz_AMOC1 + c2*(Psi_SO_Atl - psibz_ZOC1))/lbasin    (:233)
+ *                    B_ATL = (c1*Ab + c2*(iA - Zb))/lbasin                             (:234-236)
+ *                    PAC   = (c2*(Psi_SO_Pac + psibz_ZOC2))/lbasin                     (:237)
+ *                    B_PAC = (c2*(iP + Zb))/lbasin                                     (:238-239)
+ *   transition       Z = Z_ATL = Psi_AMOC;  ATL = np.interp(x, bgrid_AMOC, psib_AMOC)  (:244-248)
+ *                    B = B_ATL = Ab[k] where b_basin[k] < x[nz-1], else 0              (:247, :249)
+ *   north            Z = Z_ATL = (c3*Psi_AMOC)/lnorth;  ATL = (c3*psibz_AMOC2)/lnorth  (:254-259)
+ *                    B = B_ATL = (c3*Ab[k])/lnorth where b_basin[k] < x[nz-1], else 0  (:257-260)
+ *   transition and north: Z_PAC = B_PAC = PAC = NaN                                    (:246-262)
+ * The last row is NOT zeroed (Plot_overturning.py does that, this script does not).
+ *   bnew     = concatenate(bsouth, tile(b_basin), btrans, tile(bn))                    (:203)
+ *   bnew_Atl = ... tile(b_Atl) in the basin rows                                       (:204)
+ *   bnew_Pac = ... tile(b_Pac) in the basin rows, NaN in transition and north          (:205)
+ * c1 = ynew - lchannel, c2 = lchannel + lbasin - ynew, c3 = lchannel + lbasin + ltrans + lnorth -
+ * ynew are formed by the caller in the script's order.  IEEE fp64 in the script's operation order,
+ * `/` for its divisions, np.interp as in pm_sections_grid: bit-identical.  Inputs are pm_rows as
+ * for pm_overturning; one nb serves both thermal winds (the script: 500 for both).
+ * Every output may be NULL (not stored); extrema and status are computed regardless.
+ * extrema [n][8][2] = {max, min} per field, extrema_at their indices iy*nz + k, with the contract
+ * of pm_overturning (first occurrence; a NaN gives NaN and the first NaN's index); the three
+ * Pacific fields over the rows the script defines, field[:ny + n_basin].
+ * status bits: PM_TBO_NAN_SECTION a NaN in bsouth / btrans / bn; PM_TBO_BAD_BASIN / _BAD_ATL /
+ * _BAD_PAC b_basin / b_Atl / b_Pac non-finite or not non-decreasing; PM_TBO_BAD_BGRID_AMOC / _ZOC
+ * that bgrid not non-decreasing.  Such a member gets whatever the interpolation gives and does not
+ * disturb the others.
+ * Sizes: 2 <= nz, ny <= 1024, 1 <= nb <= 2048, n_basin, n_trans, n_north >= 1 and together <=
+ * 1024, and the member's rows must fit one workgroup's LDS: pm_twobasin_overturning_lds_bytes
+ * (17 rows of nz, one of ny, two of nb doubles, each padded to 16 bytes, plus the reduction's
+ * scratch) <= 160 KB -- nz = ny = 512 with nb = 2048 is 105 KB and runs, nz = 1024 with nb = 2048
+ * (177 KB) does not.  PM_EINVAL beyond.                                                       */
+#define PM_TBO_Z 0
+#define PM_TBO_Z_ATL 1
+#define PM_TBO_Z_PAC 2
+#define PM_TBO_B 3
+#define PM_TBO_B_ATL 4
+#define PM_TBO_B_PAC 5
+#define PM_TBO_ATL 6
+#define PM_TBO_PAC 7
+#define PM_TBO_FIELDS 8
+#define PM_TBO_NAN_SECTION 1
+#define PM_TBO_BAD_BASIN 2
+#define PM_TBO_BAD_ATL 4
+#define PM_TBO_BAD_PAC 8
+#define PM_TBO_BAD_BGRID_AMOC 16
+#define PM_TBO_BAD_BGRID_ZOC 32
+#define PM_TBO_MAX_LEVELS 1024
+#define PM_TBO_MAX_NB 2048
+typedef struct pm_twobasin_rows {
+  int32_t n, nz;
+  pm_rows b_Atl, b_Pac, b_north; /* [nz] the three columns                                   */
+  pm_rows A_Atl, A_Pac;          /* [1] the basins' areas, per member                        */
+  double *b_basin, *bn;          /* [n][nz] out                                              */
+} pm_twobasin_rows;
+typedef struct pm_twobasin_overturning {
+  int32_t n, nz, ny, nb;         /* members, levels, channel rows, isopycnal classes         */
+  int32_t n_basin, n_trans, n_north; /* the script: 60, 20, 20                               */
+  int32_t reserved;
+  pm_rows b_Atl, b_Pac;          /* [nz] Atl.b, Pac.b                                        */
+  pm_rows A_Atl, A_Pac;          /* [1]                                                      */
+  pm_rows bs_SO;                 /* [ny] raw channel surface buoyancy                        */
+  pm_rows Psi_SO_Atl, Psi_SO_Pac, Psi_AMOC, Psi_ZOC;              /* [nz]                    */
+  pm_rows psibz_AMOC1, psibz_AMOC2; /* [nz] AMOC.Psibz(nb)[0], [1]                           */
+  pm_rows psibz_ZOC1, psibz_ZOC2;   /* [nz] ZOC.Psibz()[0], [1]                              */
+  pm_rows bgrid_AMOC, psib_AMOC, bgrid_ZOC, psib_ZOC;             /* [nb]                    */
+  pm_rows bsouth;                /* [ny][nz] channel section                                 */
+  pm_rows btrans;                /* [n_trans][nz] transition section                         */
+  pm_rows bn;                    /* [nz] pm_twobasin_profiles' bn                            */
+  const double *c1, *c2, *c3;    /* [nrows] shared row coefficients                          */
+  double lbasin, lnorth;
+  double *psi[PM_TBO_FIELDS];    /* [n][nrows][nz] out, each may be NULL (not stored)        */
+  double *bnew, *bnew_Atl, *bnew_Pac; /* [n][nrows][nz] out, each may be NULL                */
+  double *extrema;               /* [n][8][2] out: {max, min} per field (may be NULL)        */
+  int32_t *extrema_at;           /* [n][8][2] out: their indices iy*nz + k (may be NULL)     */
+  int32_t *status;               /* [n] out: PM_TBO_* bits (may be NULL)                     */
+} pm_twobasin_overturning;
+
+int pm_twobasin_profiles(const pm_twobasin_rows *d, pm_stream_t stream);
+int pm_twobasin_overturning_lds_bytes(int32_t nz, int32_t ny, int32_t nb, size_t *bytes);
+int pm_twobasin_overturning_sections(const pm_twobasin_overturning *d, pm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Convergence check of an ensemble run to steady state (pymoc_amd.run_to_steady), ONE launch
  * over the n rows of the current batch.  Row m holds original member k = orig[m]; rows whose

@@ -15,6 +15,7 @@ from .equilibrium import ColumnEquiBatch
 from .equi_column import EquiColumnBatch
 from .sections import SectionBatch
 from .overturning import OverturningSections
+from .twobasin_overturning import TwoBasinOverturningSections
 from . import modules
 from . import utils
 from .modules import Column, Psi_Thermwind, Psi_SO, SO_ML, Equi_Column

@@ -180,6 +180,35 @@ class pm_overturning(C.Structure):
   ]
 
 
+PM_TBO_FIELDS = 8
+(PM_TBO_NAN_SECTION, PM_TBO_BAD_BASIN, PM_TBO_BAD_ATL, PM_TBO_BAD_PAC, PM_TBO_BAD_BGRID_AMOC,
+ PM_TBO_BAD_BGRID_ZOC) = 1, 2, 4, 8, 16, 32
+PM_TBO_MAX_LEVELS, PM_TBO_MAX_NB = 1024, 2048
+LDS_PER_CU = 160 * 1024
+
+
+class pm_twobasin_rows(C.Structure):
+  """Mirror of `struct pm_twobasin_rows` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("nz", C.c_int32), ("b_Atl", pm_rows), ("b_Pac", pm_rows),
+              ("b_north", pm_rows), ("A_Atl", pm_rows), ("A_Pac", pm_rows), ("b_basin", c_dp),
+              ("bn", c_dp)]
+
+
+class pm_twobasin_overturning(C.Structure):
+  """Mirror of `struct pm_twobasin_overturning` (include/pymoc_hip.h)."""
+  ROWS = ("b_Atl", "b_Pac", "A_Atl", "A_Pac", "bs_SO", "Psi_SO_Atl", "Psi_SO_Pac", "Psi_AMOC",
+          "Psi_ZOC", "psibz_AMOC1", "psibz_AMOC2", "psibz_ZOC1", "psibz_ZOC2", "bgrid_AMOC",
+          "psib_AMOC", "bgrid_ZOC", "psib_ZOC", "bsouth", "btrans", "bn")
+  _fields_ = [
+      ("n", C.c_int32), ("nz", C.c_int32), ("ny", C.c_int32), ("nb", C.c_int32),
+      ("n_basin", C.c_int32), ("n_trans", C.c_int32), ("n_north", C.c_int32),
+      ("reserved", C.c_int32)] + [(r, pm_rows) for r in ROWS] + [
+      ("c1", c_dp), ("c2", c_dp), ("c3", c_dp), ("lbasin", C.c_double), ("lnorth", C.c_double),
+      ("psi", c_dp * PM_TBO_FIELDS), ("bnew", c_dp), ("bnew_Atl", c_dp), ("bnew_Pac", c_dp),
+      ("extrema", c_dp), ("extrema_at", c_dp), ("status", c_dp)
+  ]
+
+
 PM_PACK_MAX_ITEMS = 8
 
 
@@ -315,6 +344,11 @@ SIGNATURES = {
                                        C.POINTER(C.c_int32)]),
     "pm_sections_grid": (C.c_int, [C.POINTER(pm_sections), C.c_void_p]),
     "pm_overturning_sections": (C.c_int, [C.POINTER(pm_overturning), C.c_void_p]),
+    "pm_twobasin_profiles": (C.c_int, [C.POINTER(pm_twobasin_rows), C.c_void_p]),
+    "pm_twobasin_overturning_lds_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32,
+                                                    C.POINTER(C.c_size_t)]),
+    "pm_twobasin_overturning_sections": (C.c_int, [C.POINTER(pm_twobasin_overturning),
+                                                   C.c_void_p]),
     "pm_steady_check": (C.c_int, [C.POINTER(pm_steady_check), C.c_void_p]),
 }
 

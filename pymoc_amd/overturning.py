@@ -7,8 +7,9 @@ that :52-71 assemble -- bit-identical, one launch of pm_overturning_sections
 (pymoc_amd/csrc/overturning.hip) for all members, plus each member's extrema of the three fields
 (how strong and where each cell is).
 
-Out of scope: the eight fields of the two-basin script (twobasin_NadeauJansen.py:207-262: two
-basins' z / b / residual sections and their sums over a transition region) are not built here.
+Out of scope here: the eight fields of the two-basin script (twobasin_NadeauJansen.py:207-262:
+two basins' z / b / residual sections and their sums over a transition region) are built by
+TwoBasinOverturningSections (pymoc_amd/twobasin_overturning.py).
 """
 import ctypes as C
 
@@ -63,7 +64,8 @@ class OverturningSections(object):
 
   compute() is one launch; psi_z / psi_b / psi_res / b are the device arrays (None when not
   stored), ynew the row coordinate in km, extrema() and status() the per-member numbers.
-  The two-basin script's fields (twobasin_NadeauJansen.py:207-262) are out of scope.
+  The two-basin script's fields (twobasin_NadeauJansen.py:207-262) are out of scope here:
+  TwoBasinOverturningSections builds them.
   """
 
   def __init__(self, y, z, nb, n=None, b_basin=None, bs_SO=None, Psi=None, Psi_SO=None,
