@@ -178,6 +178,17 @@ int pm_graph_destroy(pm_graph_t graph);
                               (below).  Fused launches then divide in 3 instead of 4 instructions;
                               results are bit-identical (the quotient is the IEEE one).           */
 
+#define PM_COLS_DIV2_GRID 4 /* pm_columns.reserved, batch-wide HINT, honoured only together with
+                              PM_COLS_DIV3_PROVEN (ignored otherwise): pm_div2_proven() and
+                              pm_recip2_check() hold for every grid spacing and centred spacing of
+                              the batch, so the fused launch divides by them with the 2-instruction
+                              exact quotient (below).  Bit-identical results.                     */
+#define PM_COL_DIV2_AREA 16 /* per-column HINT (pm_columns.flags), honoured only together with
+                              PM_COLS_DIV3_PROVEN and PM_COLS_DIV2_GRID: pm_div2_proven() and
+                              pm_recip2_check() hold for this column's Area, so all three of its
+                              quotients take the 2-instruction form.  A column without it keeps
+                              the 3-instruction quotient for the division by Area.                */
+
 typedef struct pm_columns {
   int32_t ncols;         /* independent columns in the batch                      */
   int32_t nz;            /* levels per column (2 <= nz <= 1024)                   */
@@ -662,6 +673,32 @@ int pm_div3_proven(const double *d, int64_t n, int32_t *proven, int64_t *candida
  * the kernels' prologues evaluate the same expression).  A caller sets PM_COLS_DIV3_PROVEN only
  * when both pm_div3_proven and pm_recip_check hold for the batch's denominators.               */
 int pm_recip_check(const double *d, int64_t n, int32_t *ok);
+
+/* Host function (no device work): proven[i] = 1 when the 2-instruction quotient
+ *   yh = RN(1/d); yl = RN((1 - d yh) / d); q = fma(a, yh, RN(a yl))
+ * is the correctly rounded a / d[i] for every numerator a (same operand window as above).  The last
+ * fma rounds (a/d)(1 + eta) with |eta| < 2.01 * 2^-106, so only numerators whose quotient lies within
+ * 4 / (2 D) ulp of a rounding midpoint could fail (D: d's 53-bit integer mantissa); they are
+ * enumerated as in pm_div3_proven and run through the very sequence (pymoc_hip.hip: div2_proof).
+ * There is no correction step, so some denominators DO fail (about 1 % of arbitrary mantissas; none
+ * whose mantissa has three or more trailing zero bits, which have no candidate at all): the verdict is
+ * per denominator.  `candidates` (may be NULL) receives the number of numerators tested.  What a
+ * caller establishes before it sets PM_COLS_DIV2_GRID / PM_COL_DIV2_AREA.                        */
+int pm_div2_proven(const double *d, int64_t n, int32_t *proven /* [n] */, int64_t *candidates);
+
+/* pm_recip_check's sibling for that form: ok[i] = 1 when the device's yh = 1.0 / d[i] AND its low part
+ * yl = fma(-d[i], yh, 1.0) / d[i] equal the host's bit for bit (one small launch; the kernel's
+ * prologue evaluates the same expressions).  pm_div2_proven's verdict is valid for that pair only. */
+int pm_recip2_check(const double *d, int64_t n, int32_t *ok /* [n] */);
+
+/* debug/test: the DEVICE's 2-instruction quotient against the HOST's IEEE `/` on the candidate
+ * numerators of `ndenoms` random denominators (drawn as in pm_selftest_div3; numerators of both
+ * signs, rescaled) plus two arbitrary numerators for each proven one.  `mismatches` counts the pairs
+ * whose denominator pm_div2_proven accepts and must be 0; `unproven` = denominators the proof
+ * rejected, `unproven_mismatches` the differing pairs among THEIR candidates (not zero: that is why
+ * they are rejected).                                                                            */
+int pm_selftest_div2(uint64_t seed, int32_t ndenoms, uint64_t *tested, uint64_t *mismatches,
+                     uint64_t *unproven, uint64_t *unproven_mismatches);
 
 /* debug/test: the DEVICE's 3-instruction quotient against the HOST's IEEE `/` on the candidate
  * numerators of `ndenoms` random denominators (uniform mantissas, mantissas next to 1 and 2,

@@ -27,6 +27,8 @@ PM_OP_WA_PSI = 32
 PM_OP_WA_TWOBASIN = 64
 PM_COLS_ALL_UNIFORM_AREA = 1
 PM_COLS_DIV3_PROVEN = 2
+PM_COLS_DIV2_GRID = 4
+PM_COL_DIV2_AREA = 16
 
 c_dp = C.c_void_p  # device pointers travel as plain addresses
 
@@ -337,6 +339,10 @@ SIGNATURES = {
     "pm_selftest_lane_shift": (C.c_int, [C.POINTER(C.c_int32)]),
     "pm_div3_proven": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "pm_recip_check": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
+    "pm_div2_proven": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+    "pm_recip2_check": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "pm_selftest_div2": (C.c_int, [C.c_uint64, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pm_selftest_div3": (C.c_int, [C.c_uint64, C.c_int32, C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),

@@ -52,6 +52,7 @@ def _in_fast_range(x):
 
 
 _HINT_DIV3_OFF = 1 << 20  # (use_hints(div3=False): a bit outside the per-column flag bits)
+_HINT_DIV2_OFF = 1 << 21  # (use_hints(div2=False))
 _ALIGNED_ADDRESS = 1 << 12  # stand-in for a DeviceArray's address in kernel_name (never dereferenced)
 
 
@@ -74,6 +75,21 @@ def device_reciprocals_exact(denominators):
   ok = C.c_int32(0)
   check(lib.pm_recip_check(d.ctypes.data, d.size, C.byref(ok)))
   return bool(ok.value)
+
+
+def div2_proven(denominators):
+  """Per denominator: True when the kernels' 2-instruction quotient is correctly rounded for EVERY
+  numerator over it (`pm_div2_proven`: a host-side proof by enumeration; unlike the 3-instruction
+  form it fails for about 1 % of arbitrary mantissas) AND the device forms the reciprocal pair the
+  proof assumed (`pm_recip2_check`: the device's 1.0 / d and its low part against the host's)."""
+  d = np.ascontiguousarray(denominators, dtype=np.float64).ravel()
+  proven = np.zeros(d.size, dtype=np.int32)
+  check(lib.pm_div2_proven(d.ctypes.data, d.size, proven.ctypes.data, None))
+  if proven.any():
+    ok = np.zeros(d.size, dtype=np.int32)
+    check(lib.pm_recip2_check(d.ctypes.data, d.size, ok.ctypes.data))
+    proven &= ok
+  return proven.astype(bool)
 
 
 class ColumnBatch(object):
@@ -169,6 +185,17 @@ class ColumnBatch(object):
     if self.uniform_area and ok:
       den = np.concatenate([np.unique(dz), np.unique(dzc), np.unique(area[:, 0])])
       self.div3_proven = div3_proven(den) and device_reciprocals_exact(den)
+    # PM_COLS_DIV2_GRID / PM_COL_DIV2_AREA (honoured together with PM_COLS_DIV3_PROVEN only): the
+    # 2-instruction quotient is proven per denominator -- for the grid as a whole, for the Areas
+    # column by column (`div2_area_proven`: the stored verdicts)
+    self.div2_grid_proven = False
+    self.div2_area_proven = np.zeros(ncols, dtype=bool)
+    if self.div3_proven:
+      ua_vals, inv = np.unique(area[:, 0], return_inverse=True)
+      v = div2_proven(np.concatenate([np.unique(dz), np.unique(dzc), ua_vals]))
+      self.div2_grid_proven = bool(v[:v.size - ua_vals.size].all())
+      if self.div2_grid_proven:
+        self.div2_area_proven = v[v.size - ua_vals.size:][inv.ravel()]
     if hasattr(self, "_flags_host"):
       self._upload_flags()
 
@@ -212,19 +239,26 @@ class ColumnBatch(object):
     bit = np.int32(_lib.PM_COL_UNIFORM_AREA)  # every column's Area is one number (set_static)
     self._flags_host = (self._flags_host | bit if self.uniform_area
                         else self._flags_host & ~bit).astype(np.int32)
+    bit = np.int32(_lib.PM_COL_DIV2_AREA)
+    self._flags_host = np.where(self.div2_area_proven, self._flags_host | bit,
+                                self._flags_host & ~bit).astype(np.int32)
     off = np.int32(self.__dict__.get("_hints_off", 0))
+    if off & (_HINT_DIV2_OFF | _HINT_DIV3_OFF):
+      off |= bit
     self.flags.upload((self._flags_host & ~off).astype(np.int32), self.stream)
 
-  def use_hints(self, uniform_area=True, static_in_range=True, div3=True):
+  def use_hints(self, uniform_area=True, static_in_range=True, div3=True, div2=True):
     """Switch the per-column hints the host derives from the static operands on or off
     (PM_COL_UNIFORM_AREA: a column's Area is one number, read with its scalars;
     PM_COL_STATIC_IN_RANGE: the static operands lie inside the exact-division window, so a launch
-    tests only the state and the forcing).  Without them the kernels take the C-ABI's default
+    tests only the state and the forcing; div3 / div2: the proven 3- and 2-instruction quotients of
+    fused launches, PM_COLS_DIV3_PROVEN and PM_COLS_DIV2_GRID / PM_COL_DIV2_AREA -- div3=False turns
+    both off).  Without them the kernels take the C-ABI's default
     path -- every array read, every operand tested; results are bit-identical either way.  The
     hints are re-derived whenever the static operands or parameters change."""
     self._hints_off = ((0 if uniform_area else _lib.PM_COL_UNIFORM_AREA) |
                        (0 if static_in_range else _lib.PM_COL_STATIC_IN_RANGE) |
-                       (0 if div3 else _HINT_DIV3_OFF))
+                       (0 if div3 else _HINT_DIV3_OFF) | (0 if div2 else _HINT_DIV2_OFF))
     self._upload_flags()
 
   @property
@@ -265,6 +299,8 @@ class ColumnBatch(object):
     d.reserved = _lib.PM_COLS_ALL_UNIFORM_AREA if ua else 0
     if ua and self.div3_proven and not (off & _HINT_DIV3_OFF):
       d.reserved |= _lib.PM_COLS_DIV3_PROVEN
+      if self.div2_grid_proven and not (off & _HINT_DIV2_OFF):
+        d.reserved |= _lib.PM_COLS_DIV2_GRID
     d.z, d.b = self.z.ptr, self.b.ptr
     d.kappa, d.area, d.dAkappa = self.kappa.ptr, self.area.ptr, self.dAk.ptr
     d.bs, d.bbot, d.bzbot, d.N2min = self.bs.ptr, self.bbot.ptr, self.bzbot.ptr, self.N2min.ptr

@@ -24,7 +24,8 @@ struct ColGrid {     // shared by every column of a batch (and by the columns of
   double dz[P];    // z[i+1]-z[i]           (interface above level i)
   double dzc[P];   // 0.5*(dz[i]+dz[i-1])   (column.py:238)
   double rdz[P], rdzc[P];  // RN(1/dz) (0 above the top level), RN(1/dzc)
-  double rdz_l[P], rdzc_l[P];  // low parts: RN(1/d - RN(1/d)), for div_by_recip2 (DIV == 2)
+  double rdz_l[P], rdzc_l[P];  // low parts ~ 1/d - RN(1/d): recip_lo for div_by_recip2 (DIV == 2),
+                               // recip_lo_div for the 2-instruction quotients (DIV == 7, 8)
 };
 template <int P>
 struct ColRegs {
@@ -219,7 +220,11 @@ __device__ __forceinline__ void col_convect_cached(double (&b)[P], const double 
 // needs RN(1/d)); 2: div_by_recip2 (4 instructions, needs the double-double reciprocal); 3: the
 // two divisions by grid metrics as in 1, the division by Area as in 0 (streaming kernel: the
 // grid is shared by the columns a wave walks through, the areas are not).  All are correctly
-// rounded, hence bit-identical to each other and to NumPy.
+// rounded, hence bit-identical to each other and to NumPy.  6: all three by the proven
+// 3-instruction quotient; 7: the two grid quotients by the proven 2-instruction one (needs the low
+// parts g.rdz_l / g.rdzc_l from recip_lo_div, NOT g.dz / g.dzc), Area as in 6; 8: all three in 2
+// instructions (r.rarea_lu from recip_lo_div as well).  6, 7 and 8 are chosen per wave inside
+// k_column_steps<64,P,6,...> from the caller's per-denominator proofs (plain_run).
 // BC = false: the caller has already imposed the (constant) boundary values, which no
 // interior update ever touches -- valid when bzbot is None and the surface value is bs.
 // WEFF: `wA` already holds weff = wA - d(A kappa)/dz (callers that keep it across steps).
@@ -230,7 +235,7 @@ __device__ __forceinline__ void col_convect_cached(double (&b)[P], const double 
 // compare-select flux, and boundary / padding levels left untouched by a select (the other
 // forms advance them with dt = 0, which turns a level next to an inf or NaN into NaN).
 template <int G, int P, int DIV, bool BC = true, bool WEFF = false, bool UA = false,
-          bool FLUXFMA = (DIV == 2 || DIV == 6)>
+          bool FLUXFMA = (DIV == 2 || DIV >= 6)>
 __device__ __forceinline__ void col_vertadvdiff(const ColGrid<P> &g, ColRegs<P> &r,
                                                 const double (&wA)[P],
                                                 double dt, bool do_conv, double bs,
@@ -289,6 +294,13 @@ __device__ __forceinline__ void col_vertadvdiff(const ColGrid<P> &g, ColRegs<P> 
       for (int p = 0; p < P; ++p) rr[p] = __builtin_fma(-g.dz[p], q[p], num[p]);
 #pragma unroll
       for (int p = 0; p < P; ++p) q[p] = __builtin_fma(rr[p], g.rdz[p], q[p]);
+    } else if constexpr (DIV == 7 || DIV == 8) {
+      // u = a*yl; q = fma(a, yh, u): correctly rounded for EVERY numerator when the denominator has
+      // passed pm_div2_proven (PM_COLS_DIV2_GRID; common.hip.h: div_by_recip2x)
+#pragma unroll
+      for (int p = 0; p < P; ++p) rr[p] = num[p] * g.rdz_l[p];
+#pragma unroll
+      for (int p = 0; p < P; ++p) q[p] = __builtin_fma(num[p], g.rdz[p], rr[p]);
     } else if constexpr (DIV == 6) {
       // q0 = a*y; r = fma(-d, q0, a); q = fma(r, y, q0): correctly rounded for EVERY numerator when
       // the denominator has passed pm_div3_proven (PM_COLS_DIV3_PROVEN; common.hip.h)
@@ -382,6 +394,32 @@ __device__ __forceinline__ void col_vertadvdiff(const ColGrid<P> &g, ColRegs<P> 
       bzz[p] = __builtin_fma(r1[p], g.rdzc[p], bzz[p]);
       adv[p] = __builtin_fma(r2[p], (UA ? r.rarea_u : r.rarea[p]), adv[p]);
     }
+  } else if constexpr (DIV == 8) {  // both by the proven 2-instruction quotient, interleaved
+    double r1[P], r2[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      r1[p] = dbz[p] * g.rdzc_l[p];
+      r2[p] = flx[p] * (UA ? r.rarea_lu : r.rarea_l[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      bzz[p] = __builtin_fma(dbz[p], g.rdzc[p], r1[p]);
+      adv[p] = __builtin_fma(flx[p], (UA ? r.rarea_u : r.rarea[p]), r2[p]);
+    }
+  } else if constexpr (DIV == 7) {  // bzz in 2 instructions, adv in 3, stage by stage
+    double r1[P], r2[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      r1[p] = dbz[p] * g.rdzc_l[p];
+      adv[p] = flx[p] * (UA ? r.rarea_u : r.rarea[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      bzz[p] = __builtin_fma(dbz[p], g.rdzc[p], r1[p]);
+      r2[p] = __builtin_fma(-(UA ? r.area_u : r.area[p]), adv[p], flx[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) adv[p] = __builtin_fma(r2[p], (UA ? r.rarea_u : r.rarea[p]), adv[p]);
   } else if constexpr (DIV == 5) {  // grid as DIV == 3; Area (UA: one number) by its double-double reciprocal
     double r1[P];
 #pragma unroll
@@ -803,7 +841,14 @@ __global__ __launch_bounds__(256) void k_column_steps(
     const double *__restrict__ bin_g, double dt, int nsteps, int ops) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int lg = threadIdx.x % G;
-  const int col_raw = (int)((blockIdx.x * (unsigned)blockDim.x + threadIdx.x) / G);
+  int col_raw = (int)((blockIdx.x * (unsigned)blockDim.x + threadIdx.x) / G);
+  // The instantiation that chooses among three step forms (below): a wave holds one column, and
+  // with its index as a SCALAR the column's parameters (flags, bs, bbot, bzbot, N2min) and row
+  // addresses come by scalar loads.  As per-lane values they sat in ~12 VGPRs that were live across
+  // the form switch and through every leg: 108 instead of 96 VGPRs at P = 2, 4 waves per SIMD
+  // instead of 5.
+  constexpr bool FORMS = FAST == 6 && G == 64 && P <= 2 && PLAIN;
+  if constexpr (FORMS) col_raw = __builtin_amdgcn_readfirstlane(col_raw);
   const bool col_ok = col_raw < c.ncols;
   const int col = col_ok ? col_raw : c.ncols - 1;  // idle groups shadow the last column
   const int nz = c.nz;
@@ -916,11 +961,17 @@ __global__ __launch_bounds__(256) void k_column_steps(
 
   if constexpr (FAST == 4) col_make_contracted<P>(g, r, wA, dt, lane, nz);  // (G == 64 only)
 
-  if constexpr (PLAIN) {
+  // The time loop of a launch of plain timesteps in the step form DIV: the BC-free 4-fold loop, the
+  // speculative convective loops (conv_spec_run) and the bzbot loops.  One instantiation per step
+  // form, so that <64,P,6,...> can choose among 6, 7 and 8 once per wave, before the loop.  (A generic
+  // lambda, not a function template: as a forceinline function taking g, r and wA by reference the
+  // same body cost 4 VGPRs at <64,2,2,true,true> -- 100, one wave per SIMD fewer -- and 20 at <64,2,6>.)
+  auto plain_run = [&](auto DIVC) {
+    constexpr int DIV = decltype(DIVC)::value;
     if (do_conv && use_bzbot) {
       for (int s = 0; s < nsteps; ++s) {
         col_convect<G, P>(r.b, g.z, bs, N2min, lg, lane, nz, c.z);
-        col_vertadvdiff<G, P, FAST, true, false, UA>(g, r, wA, dt, true, bs, bbot, true, bzbot, lg, nz);
+        col_vertadvdiff<G, P, DIV, true, false, UA>(g, r, wA, dt, true, bs, bbot, true, bzbot, lg, nz);
       }
     } else if (do_conv) {
       // b[0] = bbot is constant unless a convection event rewrites level 0: impose it once
@@ -932,34 +983,34 @@ __global__ __launch_bounds__(256) void k_column_steps(
       if constexpr (G == 64) {
         col_convect_cached<P>(r.b, g.z, bs, N2min, lane, nz, cc);  // step 0: establishes cc
         if (lg == 0) r.b[0] = bbot;
-        col_vertadvdiff<G, P, FAST, false, false, UA>(g, r, wA, dt, true, bs, bbot, false, 0., lg, nz);
+        col_vertadvdiff<G, P, DIV, false, false, UA>(g, r, wA, dt, true, bs, bbot, false, 0., lg, nz);
         int s = 1;
         while (s < nsteps) {  // one pass per established pattern class (rarely more than one)
           const unsigned v = conv_variant<P>(cc);
           if constexpr (P <= 2) {
             switch (v) {
-              case 0: s = conv_spec_run<P, FAST, 0u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
-              case 1: s = conv_spec_run<P, FAST, 1u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
-              case 2: s = conv_spec_run<P, FAST, 2u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
-              default: s = conv_spec_run<P, FAST, 3u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
+              case 0: s = conv_spec_run<P, DIV, 0u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
+              case 1: s = conv_spec_run<P, DIV, 1u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
+              case 2: s = conv_spec_run<P, DIV, 2u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
+              default: s = conv_spec_run<P, DIV, 3u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
             }
           } else {
             if (v == 0u)
-              s = conv_spec_run<P, FAST, 0u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps);
+              s = conv_spec_run<P, DIV, 0u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps);
             else
-              s = conv_spec_run<P, FAST, (1u << P) - 1u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps);
+              s = conv_spec_run<P, DIV, (1u << P) - 1u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps);
           }
         }
       } else {
         for (int s = 0; s < nsteps; ++s) {
           col_convect<G, P>(r.b, g.z, bs, N2min, lg, lane, nz, c.z);
           if (lg == 0) r.b[0] = bbot;  // column.py:232 (a convection event may rewrite level 0)
-          col_vertadvdiff<G, P, FAST, false, false, UA>(g, r, wA, dt, true, bs, bbot, false, 0., lg, nz);
+          col_vertadvdiff<G, P, DIV, false, false, UA>(g, r, wA, dt, true, bs, bbot, false, 0., lg, nz);
         }
       }
     } else if (use_bzbot) {
       for (int s = 0; s < nsteps; ++s)
-        col_vertadvdiff<G, P, FAST, true, false, UA>(g, r, wA, dt, false, bs, bbot, true, bzbot, lg, nz);
+        col_vertadvdiff<G, P, DIV, true, false, UA>(g, r, wA, dt, false, bs, bbot, true, bzbot, lg, nz);
     } else {
       // constant boundary values: impose them once, then run the BC-free step
 #pragma unroll
@@ -972,14 +1023,47 @@ __global__ __launch_bounds__(256) void k_column_steps(
       int s = 0;
       if constexpr (P <= 2) {
         for (; s + 4 <= nsteps; s += 4) {
-          col_vertadvdiff<G, P, FAST, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
-          col_vertadvdiff<G, P, FAST, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
-          col_vertadvdiff<G, P, FAST, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
-          col_vertadvdiff<G, P, FAST, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
+          col_vertadvdiff<G, P, DIV, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
+          col_vertadvdiff<G, P, DIV, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
+          col_vertadvdiff<G, P, DIV, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
+          col_vertadvdiff<G, P, DIV, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
         }
       }
       for (; s < nsteps; ++s)
-        col_vertadvdiff<G, P, FAST, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
+        col_vertadvdiff<G, P, DIV, false, false, UA>(g, r, wA, dt, false, bs, bbot, false, 0., lg, nz);
+    }
+  };
+  if constexpr (PLAIN) {
+    // (P <= 2 only: at P = 3 and 4 the three legs cost a wave per SIMD -- 138 / 185 VGPRs against 124 /
+    // 162 -- so those keep the 3-instruction form alone and ignore the two hints)
+    if constexpr (FORMS) {
+      // PM_COLS_DIV2_GRID (batch) / PM_COL_DIV2_AREA (this wave's column): the caller's
+      // pm_div2_proven + pm_recip2_check verdicts license the 2-instruction quotients.  The low
+      // parts are formed here, on the chosen leg only, so the other legs carry no register for them.
+      const bool d2g = (c.reserved & PM_COLS_DIV3_PROVEN) != 0 && (c.reserved & PM_COLS_DIV2_GRID) != 0;
+      if (d2g) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+          const bool below_top = lg * P + p < nz - 1;  // (0 above: bz and bzz there stay 0 / finite)
+          g.rdz_l[p] = below_top ? recip_lo_div(g.dz[p], g.rdz[p]) : 0.0;
+          g.rdzc_l[p] = below_top ? recip_lo_div(g.dzc[p], g.rdzc[p]) : 0.0;
+        }
+        if (__builtin_amdgcn_readfirstlane(flags & PM_COL_DIV2_AREA) != 0) {
+          if constexpr (UA) {
+            r.rarea_lu = lane_value(recip_lo_div(r.area_u, r.rarea_u), 0);
+          } else {
+#pragma unroll
+            for (int p = 0; p < P; ++p) r.rarea_l[p] = recip_lo_div(r.area[p], r.rarea[p]);
+          }
+          plain_run(std::integral_constant<int, 8>{});
+        } else {
+          plain_run(std::integral_constant<int, 7>{});
+        }
+      } else {
+        plain_run(std::integral_constant<int, 6>{});
+      }
+    } else {
+      plain_run(std::integral_constant<int, FAST>{});
     }
   } else {
     for (int s = 0; s < nsteps; ++s) {

@@ -118,6 +118,22 @@ __device__ __forceinline__ double div_by_recip3(double a, double d, double yh) {
   return q;
 }
 
+// The same quotient in 2 instructions: the first two of div_by_recip2, q = RN(a yh + RN(a yl)), with
+// the low part yl = RN((1 - d yh) / d) (recip_lo_div: a true division, one rounding instead of
+// recip_lo's two).  q is RN(a/d) unless a/d lies within 2.01 * 2^-106 |a/d| of a rounding midpoint,
+// which for a GIVEN d leaves a few numerators (pymoc_hip.hip: div2_proof derives the bound,
+// enumerates them and runs this sequence on each).  Used only for STATIC denominators that have
+// passed that proof and whose device-side yh AND yl the host has checked (pm_div2_proven,
+// pm_recip2_check; PM_COLS_DIV2_GRID / PM_COL_DIV2_AREA).
+__device__ __forceinline__ double recip_lo_div(double d, double yh) {
+  const double e = __builtin_fma(-d, yh, 1.0);  // exact (see recip_lo)
+  return e / d;
+}
+__device__ __forceinline__ double div_by_recip2x(double a, double yh, double yl) {
+  const double u = a * yl;
+  return __builtin_fma(a, yh, u);
+}
+
 // Operand window of the forms above.  With every input of a column step (state, forcing,
 // coefficients, grid spacings, dt) either zero or of magnitude in [2^-200, 2^200], every
 // quotient, product and residual of the step stays at least 2^-600 and at most 2^1000 in

@@ -187,6 +187,28 @@ __global__ void k_recip(const double *__restrict__ d, size_t n, double *__restri
     y[i] = 1.0 / d[i];
 }
 
+// yh[i] = 1.0 / d[i] and yl[i] = recip_lo_div(d[i], yh[i]) as k_column_steps' prologue forms the
+// pair for its 2-instruction quotients
+__global__ void k_recip2(const double *__restrict__ d, size_t n, double *__restrict__ yh,
+                         double *__restrict__ yl) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
+       i += (size_t)gridDim.x * blockDim.x) {
+    const double y = 1.0 / d[i];
+    yh[i] = y;
+    yl[i] = recip_lo_div(d[i], y);
+  }
+}
+// the 2-instruction quotient (col_vertadvdiff's DIV == 7 / 8) of n operand pairs, reciprocal pair
+// formed as in k_recip2
+__global__ void k_selftest_div2(const double *__restrict__ a, const double *__restrict__ d, size_t n,
+                                double *__restrict__ q2) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
+       i += (size_t)gridDim.x * blockDim.x) {
+    const double y = 1.0 / d[i];
+    q2[i] = div_by_recip2x(a[i], y, recip_lo_div(d[i], y));
+  }
+}
+
 __global__ void k_twobasin_forcing(size_t count, const double *__restrict__ iso_A,
                                    const double *__restrict__ zon_A,
                                    const double *__restrict__ so_A,
@@ -222,23 +244,28 @@ static double div3_host(double a, double d, double y) {
   const double r = __builtin_fma(-d, q0, a);
   return __builtin_fma(r, y, q0);
 }
-// 1: proven; 0: not (a candidate fails, or d is zero / subnormal / not finite).  cand: if given,
-// receives the candidate numerators (scaled to d's binade), ncand their count.
-int div3_proof(double d, std::vector<double> *cand, long long *ncand) {
+// The numerators that could fail for the denominator d: mantissas A with 0 < |N| <= nmax (nmax <= 7),
+// handed to test(a, dm) as doubles a = A next to dm = D (d's mantissa as a double: the sequences are
+// invariant under powers of two inside the operand window).  1: every test passed (or there was
+// nothing to test); 0: a test failed, or d is zero / subnormal / not finite.  cand: if given, receives
+// the candidates, ncand their count.
+template <class Test>
+static int div_candidates_pass(double d, int nmax, Test test, std::vector<double> *cand,
+                               long long *ncand) {
   const double ad = d < 0 ? -d : d;
   if (!(ad >= 2.2250738585072014e-308 && ad <= 1.7976931348623157e308)) return 0;
   int e;
   const double m = frexp(ad, &e);                      // ad = m 2^e, m in [0.5, 1)
   const uint64_t D = (uint64_t)ldexp(m, 53);           // 53-bit mantissa
   const double dm = ldexp(m, 53);                      // the denominator the tests run on
-  const double y = 1.0 / dm;
   const int v = __builtin_ctzll(D);
-  if (v >= 3) return 1;                                // |N| <= 6 has no multiple of 2^v: no candidate
+  if (v >= 3) return 1;                                // |N| <= 7 has no multiple of 2^v: no candidate
   const uint64_t Dp = D >> v;
   if (Dp == 1) return 1;                               // a power of two
+  int ok = 1;
   for (int t = 0; t < 2; ++t) {
     const int sh = 53 + t;
-    for (int N = -6; N <= 6; ++N) {
+    for (int N = -nmax; N <= nmax; ++N) {
       if (N == 0 || (N % (1 << v)) != 0) continue;
       const int64_t Np = N / (1 << v);
       uint64_t x = (uint64_t)(((Np % (int64_t)Dp) + (int64_t)Dp) % (int64_t)Dp);
@@ -251,11 +278,51 @@ int div3_proof(double d, std::vector<double> *cand, long long *ncand) {
         const double a = (double)A;
         if (ncand) ++*ncand;
         if (cand) cand->push_back(a);
-        if (div3_host(a, dm, y) != a / dm || div3_host(-a, dm, y) != -a / dm) return 0;
+        if (!test(a, dm)) ok = 0;  // (keeps enumerating: cand / ncand are the whole set)
       }
     }
   }
-  return 1;
+  return ok;
+}
+int div3_proof(double d, std::vector<double> *cand, long long *ncand) {
+  return div_candidates_pass(
+      d, 6,
+      [](double a, double dm) {
+        const double y = 1.0 / dm;
+        return div3_host(a, dm, y) == a / dm && div3_host(-a, dm, y) == -a / dm;
+      },
+      cand, ncand);
+}
+
+// ---- the 2-instruction exact quotient by a static denominator, and its proof per denominator.
+//   yh = RN(1/d);  yl = RN(e / d) with e = 1 - d yh (exact in one fma, |e| <= u = 2^-53);
+//   u1 = RN(a yl);  q = RN(a yh + u1) (one fma)
+// (common.hip.h: recip_lo_div, div_by_recip2x).  With yl = (e/d)(1 + d1) and u1 = a yl (1 + d2),
+// |d1|, |d2| <= u, and yh = (1 - e)/d, the last fma rounds
+//   s = a yh + u1 = x (1 - e) + x e (1 + d1)(1 + d2) = x (1 + eta),  x = a/d,
+//   eta = e (d1 + d2 + d1 d2),  |eta| <= u^2 (2 + u) < 2.01 * 2^-106.
+// x has a mantissa below 2^53 ulp, so |s - x| < 2.01 * 2^-53 ulp, and q = RN(s) = RN(x) unless a
+// rounding midpoint lies between x and s.  In div3_proof's terms x - midpoint = N / (2 D) ulp with
+// D < 2^53, i.e. more than |N| 2^-54 ulp: only numerators with |N| <= 4 can fail (|N| 2^-54 <
+// 2.01 * 2^-53), none at all when D has three or more trailing zero bits.  div2_proof enumerates
+// them with div3_proof's enumeration and runs the very sequence on each, both signs.  Unlike the
+// 3-instruction form this one DOES fail for some denominators (about 1 % of uniform mantissas:
+// there is no correction step, so a quotient 1 / (2 D) ulp off a midpoint on the wrong side of s
+// stays wrong); those keep the 3-instruction form.  The verdict holds for the yh and yl formed
+// here: the host's IEEE quotients, which the device must reproduce bit for bit (pm_recip2_check).
+static double div2_host(double a, double yh, double yl) {
+  const double u1 = a * yl;
+  return __builtin_fma(a, yh, u1);
+}
+int div2_proof(double d, std::vector<double> *cand, long long *ncand) {
+  return div_candidates_pass(
+      d, 4,
+      [](double a, double dm) {
+        const double yh = 1.0 / dm;
+        const double yl = __builtin_fma(-dm, yh, 1.0) / dm;
+        return div2_host(a, yh, yl) == a / dm && div2_host(-a, yh, yl) == -a / dm;
+      },
+      cand, ncand);
 }
 
 }  // namespace pm
@@ -1005,6 +1072,105 @@ int pm_recip_check(const double *d, int64_t n, int32_t *ok) {
     const double h = 1.0 / d[i];  // the host's correctly rounded quotient
     if (memcmp(&h, &y[(size_t)i], sizeof(double)) != 0) *ok = 0;
   }
+  return PM_OK;
+}
+
+int pm_div2_proven(const double *d, int64_t n, int32_t *proven, int64_t *candidates) {
+  PM_REQUIRE(n == 0 || (d && proven), "d or proven is NULL");
+  long long nc = 0;
+  for (int64_t i = 0; i < n; ++i) proven[i] = div2_proof(d[i], nullptr, &nc);
+  if (candidates) *candidates = nc;
+  return PM_OK;
+}
+
+int pm_recip2_check(const double *d, int64_t n, int32_t *ok) {
+  PM_REQUIRE(n == 0 || (d && ok), "d or ok is NULL");
+  if (n == 0) return PM_OK;
+  double *dd = nullptr, *dy = nullptr;
+  PM_HIP(hipMalloc((void **)&dd, (size_t)n * sizeof(double)));
+  PM_HIP(hipMalloc((void **)&dy, 2 * (size_t)n * sizeof(double)));
+  hipStream_t s = resolve_stream(nullptr);
+  PM_HIP(hipMemcpyAsync(dd, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_recip2, dim3(256), dim3(256), 0, s, dd, (size_t)n, dy, dy + n);
+  PM_HIP(hipGetLastError());
+  std::vector<double> y(2 * (size_t)n);
+  PM_HIP(hipMemcpyAsync(y.data(), dy, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  PM_HIP(hipStreamSynchronize(s));
+  PM_HIP(hipFree(dd));
+  PM_HIP(hipFree(dy));
+  for (int64_t i = 0; i < n; ++i) {
+    const double yh = 1.0 / d[i];  // the host's correctly rounded quotients: div2_proof's pair
+    const double yl = __builtin_fma(-d[i], yh, 1.0) / d[i];
+    ok[i] = memcmp(&yh, &y[(size_t)i], sizeof(double)) == 0 &&
+            memcmp(&yl, &y[(size_t)(n + i)], sizeof(double)) == 0;
+  }
+  return PM_OK;
+}
+
+int pm_selftest_div2(uint64_t seed, int32_t ndenoms, uint64_t *tested, uint64_t *mismatches,
+                     uint64_t *unproven, uint64_t *unproven_mismatches) {
+  PM_REQUIRE(tested && mismatches && unproven && unproven_mismatches, "NULL output");
+  PM_REQUIRE(ndenoms >= 1 && ndenoms <= (1 << 22), "ndenoms must be in [1, 2^22]");
+  std::vector<double> ha, hd, c;
+  std::vector<char> hp;  // the pair's denominator passed the host proof
+  unsigned long long st = seed ? seed : 1, nun = 0;
+  auto next = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return st; };
+  for (int i = 0; i < ndenoms; ++i) {
+    // mantissas as in pm_selftest_div3: uniform, a few units in the last place off 1 or 2, or with
+    // one or two trailing zero bits
+    const unsigned long long r = next();
+    uint64_t D = (1ull << 52) | (next() >> 12);
+    const int kind = (int)(r & 7);
+    if (kind == 0) D = (1ull << 52) + 1 + (next() & 1023);
+    if (kind == 1) D = (1ull << 53) - 1 - (next() & 1023);
+    if (kind == 2) D &= ~1ull;
+    if (kind == 3) D &= ~3ull;
+    const double d = ldexp((double)D, -52 + (int)((r >> 8) % 41) - 20);
+    c.clear();
+    long long nc = 0;
+    const int ok = div2_proof(d, &c, &nc);
+    if (!ok) ++nun;
+    const double scale = ldexp(1.0, (int)((r >> 16) % 41) - 20);
+    for (double a : c) {
+      for (int sgn = 0; sgn < 2; ++sgn) {
+        ha.push_back((sgn ? -a : a) * scale);
+        hd.push_back(d);
+        hp.push_back((char)ok);
+      }
+    }
+    if (ok) {  // and two arbitrary numerators
+      for (int k = 0; k < 2; ++k) {
+        ha.push_back(ldexp((double)((1ull << 52) | (next() >> 12)), -40 - (int)(next() % 30)));
+        hd.push_back(d);
+        hp.push_back(1);
+      }
+    }
+  }
+  const size_t n = ha.size();
+  double *da = nullptr, *dd = nullptr, *dq = nullptr;
+  PM_HIP(hipMalloc((void **)&da, n * sizeof(double)));
+  PM_HIP(hipMalloc((void **)&dd, n * sizeof(double)));
+  PM_HIP(hipMalloc((void **)&dq, n * sizeof(double)));
+  hipStream_t s = resolve_stream(nullptr);
+  PM_HIP(hipMemcpyAsync(da, ha.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
+  PM_HIP(hipMemcpyAsync(dd, hd.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_selftest_div2, dim3(256), dim3(256), 0, s, da, dd, n, dq);
+  PM_HIP(hipGetLastError());
+  std::vector<double> hq(n);
+  PM_HIP(hipMemcpyAsync(hq.data(), dq, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  PM_HIP(hipStreamSynchronize(s));
+  PM_HIP(hipFree(da));
+  PM_HIP(hipFree(dd));
+  PM_HIP(hipFree(dq));
+  unsigned long long bad = 0, ubad = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const double q = ha[i] / hd[i];  // the host's IEEE quotient: the reference
+    if (memcmp(&q, &hq[i], sizeof(double)) != 0) ++(hp[i] ? bad : ubad);
+  }
+  *tested = n;
+  *mismatches = bad;
+  *unproven = nun;
+  *unproven_mismatches = ubad;
   return PM_OK;
 }
 
