@@ -155,8 +155,9 @@ int pm_graph_destroy(pm_graph_t graph);
                                 in Sv; the kernel forms the driver's forcing itself,
                                   wA_Atl = (iso_A + zon_A - SO_A) * 1e6,  wA_north = -iso_N * 1e6,
                                   wA_Pac = (-zon_P - SO_P) * 1e6   (twobasin_NadeauJansen.py:103-105)
-                                -- pm_twobasin_forcing's operations, without that launch.  Launches
-                                of >= 3 steps.                                                     */
+                                -- pm_twobasin_forcing's operations, without that launch.  Each of
+                                the three arrays is read in its 2n rows only (a Pacific column takes
+                                nothing from `wA`).  Launches of >= 3 steps.                       */
 #define PM_OP_CONTRACTED 16  /* modifier, OPT-IN tolerance mode: launches of >= 3 plain timesteps
                                 (one wave per column, nz <= 256) use the contracted update
                                 b_i += cu_i (b_{i+1}-b_i) + cl_i (b_i-b_{i-1}) with per-launch

@@ -872,7 +872,10 @@ __global__ __launch_bounds__(256) void k_column_steps(
   load_levels<P>(r.b, c.b + base, lg, nz);
 #pragma unroll
   for (int p = 0; p < P; ++p) wA[p] = vdx[p] = bin[p] = 0.0;
-  if (wA_g) load_levels<P>(wA, wA_g + base, lg, nz);
+  // (PM_OP_WA_TWOBASIN: wA_g has the Atlantic and the northern columns' rows only, [2 ncols / 3][nz];
+  // a Pacific column has no row there and takes nothing from it)
+  const bool wA_row = !(PLAIN && (ops & PM_OP_WA_TWOBASIN) != 0 && col >= 2 * (c.ncols / 3));
+  if (wA_g && wA_row) load_levels<P>(wA, wA_g + base, lg, nz);
   if constexpr (PLAIN) {
     if (ops & PM_OP_WA_PSI) {
       // the two-column drivers' forcing from the overturning itself (example_twocol_plusSO.py:
@@ -900,6 +903,7 @@ __global__ __launch_bounds__(256) void k_column_steps(
       // the two-basin driver's forcing (twobasin_NadeauJansen.py:103-105; pm_twobasin_forcing's
       // operations): wA_g / vdx_g / bin_g = the AMOC's, the zonal overturning's isopycnal
       // overturnings and the two sectors' Psi_SO, [2 ncols / 3][nz] each; wA holds wA_g's row
+      // (Atlantic and northern columns)
       const int third = c.ncols / 3;
       if (col < third) {  // Atlantic: (iso_A + zon_A - SO_A) * 1e6
         double zon[P], pso[P];

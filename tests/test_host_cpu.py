@@ -102,6 +102,54 @@ def test_cabi_rejects_bad_arguments_before_touching_the_device():
   assert L.pm_equi_column_scratch_doubles(64) >= 64 * 100
 
 
+def test_cabi_rejects_bad_forcing_modifier_calls():
+  """pm_column_steps with PM_OP_WA_TWOBASIN / PM_OP_WA_PSI on calls that are wrong in exactly one
+  way: PM_EINVAL and the modifier's name in the message, before anything is launched (the stand-in
+  pointers are never dereferenced).  The call they are all derived from is accepted
+  (pm_column_kernel_name: the same checks, no launch)."""
+  from pymoc_amd import _lib
+  L, C = _lib.lib, ctypes
+  A = 0x10000
+  T, WEFF, CT = _lib.PM_OP_TIMESTEP, _lib.PM_OP_WEFF, _lib.PM_OP_CONTRACTED
+  PSI, TWO = _lib.PM_OP_WA_PSI, _lib.PM_OP_WA_TWOBASIN
+
+  def cols(ncols):
+    c = _lib.pm_columns()
+    c.ncols, c.nz, c.nsel = ncols, 10, 1
+    c.z = c.b = c.kappa = c.area = c.dAkappa = c.bs = c.bbot = c.N2min = c.flags = A
+    return c
+
+  def accepted(ncols, vdx, nsteps, ops):
+    buf = C.create_string_buffer(96)
+    c = cols(ncols)
+    return L.pm_column_kernel_name(C.byref(c), A, vdx, nsteps, ops, 0, buf, 96) == _lib.PM_OK and buf.value != b""
+
+  def refused(ncols, vdx, nsteps, ops, word, wA=A, b_in=A):
+    c = cols(ncols)
+    rc = L.pm_column_steps(C.byref(c), wA, vdx, b_in, 1., nsteps, ops, 0, None)
+    return rc == _lib.PM_EINVAL and word in L.pm_last_error().decode()
+
+  # the two-basin modifier: a three-column ensemble, >= 3 plain steps, three arrays
+  assert accepted(6, A, 3, T | TWO) and accepted(6, A, 3, T | TWO | CT)
+  assert refused(7, A, 3, T | TWO, "PM_OP_WA_TWOBASIN")   # ncols % 3 != 0
+  assert refused(8, A, 3, T | TWO, "PM_OP_WA_TWOBASIN")
+  assert refused(6, A, 2, T | TWO, "PM_OP_WA_TWOBASIN")   # nsteps < 3
+  assert refused(6, A, 1, T | TWO, "PM_OP_WA_TWOBASIN")
+  assert refused(6, None, 3, T | TWO, "PM_OP_WA_TWOBASIN")  # vdx_in = NULL
+  assert refused(6, A, 3, T | TWO | WEFF, "PM_OP_WA_TWOBASIN")
+  assert refused(6, A, 3, T | TWO | PSI, "PM_OP_WA_TWOBASIN")
+  assert refused(6, A, 3, _lib.PM_OP_VERTADVDIFF | TWO, "PM_OP_WA_TWOBASIN")  # not a whole timestep
+  assert refused(6, A, 3, T | TWO, "wA", wA=None)
+  assert refused(6, A, 3, T | TWO, "b_in", b_in=None)
+  # the two-column modifier: an even number of columns, >= 3 plain steps, no horadv slot
+  assert accepted(6, None, 3, T | PSI) and accepted(6, None, 3, T | PSI | CT)
+  assert refused(7, None, 3, T | PSI, "PM_OP_WA_PSI")     # odd ncols
+  assert refused(6, A, 3, T | PSI, "PM_OP_WA_PSI")        # vdx_in given
+  assert refused(6, None, 2, T | PSI, "PM_OP_WA_PSI")
+  assert refused(6, None, 3, T | PSI | WEFF, "PM_OP_WA_PSI")
+  assert refused(6, None, 3, T | PSI, "wA", wA=None)
+
+
 def test_cabi_bad_argument_table_of_the_per_member_entries():
   """Every per-member entry point against descriptors that are wrong in exactly one way (each
   shape limit from both sides, each required pointer NULL, bad ops, sizes that disagree between
