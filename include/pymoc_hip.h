@@ -661,7 +661,7 @@ int pm_selftest_fastdiv(uint64_t seed, int32_t blocks, int32_t per_thread, int32
  * correctly rounded a / d for every numerator a (finite operands whose quotient and residual stay
  * normal).  Only numerators whose quotient lies within 3 * 2^-53 ulp of a rounding boundary could
  * fail; for a given d they are the <= ~12 solutions of a congruence on the integer mantissas,
- * which the function enumerates and runs through the very sequence (pymoc_hip.hip: div3_proof).
+ * which the function enumerates and runs through the very sequence (div_proof.h: div3_proof).
  * Zero, subnormal and non-finite denominators are "not proven".  `candidates` (may be NULL)
  * receives the number of numerators tested.  What a caller establishes before it sets
  * PM_COLS_DIV3_PROVEN.  Replaces nothing of the reference (which divides in NumPy); it licenses
@@ -680,7 +680,7 @@ int pm_recip_check(const double *d, int64_t n, int32_t *ok);
  * is the correctly rounded a / d[i] for every numerator a (same operand window as above).  The last
  * fma rounds (a/d)(1 + eta) with |eta| < 2.01 * 2^-106, so only numerators whose quotient lies within
  * 4 / (2 D) ulp of a rounding midpoint could fail (D: d's 53-bit integer mantissa); they are
- * enumerated as in pm_div3_proven and run through the very sequence (pymoc_hip.hip: div2_proof).
+ * enumerated as in pm_div3_proven and run through the very sequence (div_proof.h: div2_proof).
  * There is no correction step, so some denominators DO fail (about 1 % of arbitrary mantissas; none
  * whose mantissa has three or more trailing zero bits, which have no candidate at all): the verdict is
  * per denominator.  `candidates` (may be NULL) receives the number of numerators tested.  What a

@@ -77,6 +77,13 @@ def device_reciprocals_exact(denominators):
   return bool(ok.value)
 
 
+def div3_licensed(denominators):
+  """True when the kernels may take the 3-instruction quotient over these denominators: the proof
+  holds for each (`div3_proven`) AND the device's reciprocals are the ones the proof assumed
+  (`device_reciprocals_exact`)."""
+  return div3_proven(denominators) and device_reciprocals_exact(denominators)
+
+
 def div2_proven(denominators):
   """Per denominator: True when the kernels' 2-instruction quotient is correctly rounded for EVERY
   numerator over it (`pm_div2_proven`: a host-side proof by enumeration; unlike the 3-instruction
@@ -184,7 +191,7 @@ class ColumnBatch(object):
     self.div3_proven = False
     if self.uniform_area and ok:
       den = np.concatenate([np.unique(dz), np.unique(dzc), np.unique(area[:, 0])])
-      self.div3_proven = div3_proven(den) and device_reciprocals_exact(den)
+      self.div3_proven = div3_licensed(den)
     # PM_COLS_DIV2_GRID / PM_COL_DIV2_AREA (honoured together with PM_COLS_DIV3_PROVEN only): the
     # 2-instruction quotient is proven per denominator -- for the grid as a whole, for the Areas
     # column by column (`div2_area_proven`: the stored verdicts)

@@ -29,6 +29,21 @@ int fail(int code, const char *fmt, ...);
 
 hipStream_t resolve_stream(pm_stream_t s);
 
+// Device scratch of one call: a hipMalloc that every return path frees (hipFree's own error is
+// ignored).  `if (const int rc = buf.alloc(count)) return rc;` reports like PM_HIP.
+template <class T>
+struct DeviceScratch {
+  T *p = nullptr;
+  DeviceScratch() = default;
+  DeviceScratch(const DeviceScratch &) = delete;
+  DeviceScratch &operator=(const DeviceScratch &) = delete;
+  ~DeviceScratch() { (void)hipFree(p); }  // (nullptr: a no-op)
+  int alloc(size_t count) {
+    PM_HIP(hipMalloc((void **)&p, count * sizeof(T)));
+    return PM_OK;
+  }
+};
+
 // ------------------------------------------------------------- lane primitives
 constexpr int WAVE = 64;
 
@@ -108,7 +123,7 @@ __device__ __forceinline__ double div_by_recip2(double a, double d, double yh, d
 // The same quotient in 3 instructions from RN(1/d) alone.  q0 may be 1.5 ulp off, so this is NOT
 // covered by the theorem above for an arbitrary denominator -- but for a GIVEN d only the few
 // numerators whose quotient lies within 3 * 2^-53 ulp of a rounding boundary could fail, and the
-// host enumerates and tests them (pm_div3_proven, pymoc_hip.hip: div3_proof).  Used only for
+// host enumerates and tests them (pm_div3_proven, div_proof.h: div3_proof).  Used only for
 // STATIC denominators that have passed that proof (PM_COLS_DIV3_PROVEN / PM_JN_DIV3_PROVEN) and
 // whose device-side reciprocal the host has checked (pm_recip_check).
 __device__ __forceinline__ double div_by_recip3(double a, double d, double yh) {
@@ -121,7 +136,7 @@ __device__ __forceinline__ double div_by_recip3(double a, double d, double yh) {
 // The same quotient in 2 instructions: the first two of div_by_recip2, q = RN(a yh + RN(a yl)), with
 // the low part yl = RN((1 - d yh) / d) (recip_lo_div: a true division, one rounding instead of
 // recip_lo's two).  q is RN(a/d) unless a/d lies within 2.01 * 2^-106 |a/d| of a rounding midpoint,
-// which for a GIVEN d leaves a few numerators (pymoc_hip.hip: div2_proof derives the bound,
+// which for a GIVEN d leaves a few numerators (div_proof.h: div2_proof derives the bound,
 // enumerates them and runs this sequence on each).  Used only for STATIC denominators that have
 // passed that proof and whose device-side yh AND yl the host has checked (pm_div2_proven,
 // pm_recip2_check; PM_COLS_DIV2_GRID / PM_COL_DIV2_AREA).

@@ -1,9 +1,9 @@
-// pymoc_hip.hip -- the single translation unit of libpymoc_hip.so: runtime plumbing
-// (memory, streams, events, graphs) and the extern "C" launchers of every kernel.
+// pymoc_hip.hip -- libpymoc_hip.so's runtime plumbing (errors, memory, streams, events, graphs,
+// RCCL), the extern "C" launchers of the column, thermal-wind, Psi_SO, SO mixed-layer and coupled-run
+// kernels and the self tests of their lane primitives; the other families are units of their own.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include <stdarg.h>
 #include <math.h>
-#include <vector>
 #include <dlfcn.h>
 #include "common.hip.h"
 #include "column.hip.h"
@@ -125,90 +125,6 @@ __global__ void k_selftest_so_scans(int nhas, unsigned long long seed, double *o
   if (ibad) atomicAdd(out_int, 1);
 }
 
-// ---- fast exact division self test -----------------------------------------------
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long &x) {
-  x += 0x9E3779B97F4A7C15ull;
-  unsigned long long z = x;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ double random_double(unsigned long long &st, int emax) {
-  const unsigned long long r = splitmix64(st);
-  unsigned long long mant = r & 0xFFFFFFFFFFFFFull;
-  const unsigned kind = (unsigned)(r >> 60) & 7u;  // 3/8 of the draws: edge mantissas
-  if (kind == 0) mant = 0xFFFFFFFFFFFFFull - ((r >> 52) & 15ull);
-  if (kind == 1) mant = (r >> 52) & 15ull;
-  if (kind == 2) mant = 0x8000000000000ull + ((r >> 52) & 15ull) - 8ull;
-  const unsigned long long r2 = splitmix64(st);
-  const int e = (int)(r2 % (unsigned long long)(2 * emax + 1)) - emax;
-  const unsigned long long bits = ((r2 >> 63) << 63) | ((unsigned long long)(1023 + e) << 52) | mant;
-  return __longlong_as_double((long long)bits);
-}
-__global__ void k_selftest_fastdiv(unsigned long long seed, int per_thread, int emax,
-                                   unsigned long long *mismatch) {
-  unsigned long long st = seed + 0x1234567ull * (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x);
-  unsigned long long bad = 0;
-  for (int i = 0; i < per_thread; ++i) {
-    const double d = random_double(st, emax);
-    const double y = 1.0 / d;
-    const double yl = recip_lo(d, y);
-    // several numerators per denominator, as in the kernels (static d, changing a); both
-    // reciprocal forms (5 instructions from RN(1/d), 4 from the double-double reciprocal)
-    for (int k = 0; k < 4; ++k) {
-      const double a = random_double(st, emax);
-      const double q_ref = a / d;
-      const double q_fast = div_by_recip(a, d, y);
-      const double q_fast2 = div_by_recip2(a, d, y, yl);
-      bad += (__double_as_longlong(q_ref) != __double_as_longlong(q_fast)) ? 1ull : 0ull;
-      bad += (__double_as_longlong(q_ref) != __double_as_longlong(q_fast2)) ? 1ull : 0ull;
-    }
-  }
-  if (bad) atomicAdd(mismatch, bad);
-}
-
-// the 3-instruction quotient (col_vertadvdiff's DIV == 6) and the device's own `/` of n operand
-// pairs (the host compares both with ITS IEEE quotient)
-__global__ void k_selftest_div3(const double *__restrict__ a, const double *__restrict__ d, size_t n,
-                                double *__restrict__ q3, double *__restrict__ qd) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const double y = 1.0 / d[i];
-    double q = a[i] * y;
-    const double r = __builtin_fma(-d[i], q, a[i]);
-    q3[i] = __builtin_fma(r, y, q);
-    qd[i] = a[i] / d[i];
-  }
-}
-// y[i] = 1.0 / d[i] as every kernel's prologue forms its reciprocals
-__global__ void k_recip(const double *__restrict__ d, size_t n, double *__restrict__ y) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x)
-    y[i] = 1.0 / d[i];
-}
-
-// yh[i] = 1.0 / d[i] and yl[i] = recip_lo_div(d[i], yh[i]) as k_column_steps' prologue forms the
-// pair for its 2-instruction quotients
-__global__ void k_recip2(const double *__restrict__ d, size_t n, double *__restrict__ yh,
-                         double *__restrict__ yl) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const double y = 1.0 / d[i];
-    yh[i] = y;
-    yl[i] = recip_lo_div(d[i], y);
-  }
-}
-// the 2-instruction quotient (col_vertadvdiff's DIV == 7 / 8) of n operand pairs, reciprocal pair
-// formed as in k_recip2
-__global__ void k_selftest_div2(const double *__restrict__ a, const double *__restrict__ d, size_t n,
-                                double *__restrict__ q2) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const double y = 1.0 / d[i];
-    q2[i] = div_by_recip2x(a[i], y, recip_lo_div(d[i], y));
-  }
-}
-
 __global__ void k_twobasin_forcing(size_t count, const double *__restrict__ iso_A,
                                    const double *__restrict__ zon_A,
                                    const double *__restrict__ so_A,
@@ -222,107 +138,6 @@ __global__ void k_twobasin_forcing(size_t count, const double *__restrict__ iso_
     wA_N[i] = (-iso_N[i]) * 1e6;                       // :104
     wA_P[i] = (-zon_P[i] - so_P[i]) * 1e6;             // :105
   }
-}
-
-// ---- the 3-instruction exact quotient by a static denominator, and its proof per denominator.
-//   y = RN(1/d);   q0 = RN(a y);   r = RN(a - d q0) (one fma);   q = RN(q0 + r y) (one fma)
-// With y = (1/d)(1 + e), |e| <= 2^-53, q0 lies within 1.5 ulp of x = a/d and the last fma rounds
-// x + delta with |delta| <= |x - q0| (2 |e| + ...) < 3 * 2^-53 ulp (the residual may itself be
-// rounded when q0 is more than an ulp off).  So q = RN(x) unless x lies within 3 * 2^-53 ulp of a
-// rounding boundary, a midpoint (2K + 1) 2^(e-53) of two neighbours.  With 53-bit integer
-// mantissas A, D of a, d:  x - midpoint = N / (2 D) ulp,  N = A 2^(53+t) - (2K + 1) D  (t = 0 for
-// A >= D, 1 for A < D), an integer -- so only numerators with |N| <= 6 can fail, and for a GIVEN
-// D these are the few solutions A of  A 2^(53+t) = N (mod D)  with an odd quotient (none at all
-// when D has three or more trailing zero bits, as every difference of two grid levels has).
-// div3_proof enumerates them and runs the very sequence on each, both signs: all equal to `/` =
-// the quotient is correctly rounded for EVERY numerator (finite operands whose quotient and
-// residual stay normal: the kernels' operand window, in_fast_div_range).  No denominator has
-// failed in 10^8 tried (the cases that could are where q0 is a faithful quotient anyway), but the
-// kernels take the 3-instruction form only on this proof, never on statistics.
-static double div3_host(double a, double d, double y) {
-  const double q0 = a * y;
-  const double r = __builtin_fma(-d, q0, a);
-  return __builtin_fma(r, y, q0);
-}
-// The numerators that could fail for the denominator d: mantissas A with 0 < |N| <= nmax (nmax <= 7),
-// handed to test(a, dm) as doubles a = A next to dm = D (d's mantissa as a double: the sequences are
-// invariant under powers of two inside the operand window).  1: every test passed (or there was
-// nothing to test); 0: a test failed, or d is zero / subnormal / not finite.  cand: if given, receives
-// the candidates, ncand their count.
-template <class Test>
-static int div_candidates_pass(double d, int nmax, Test test, std::vector<double> *cand,
-                               long long *ncand) {
-  const double ad = d < 0 ? -d : d;
-  if (!(ad >= 2.2250738585072014e-308 && ad <= 1.7976931348623157e308)) return 0;
-  int e;
-  const double m = frexp(ad, &e);                      // ad = m 2^e, m in [0.5, 1)
-  const uint64_t D = (uint64_t)ldexp(m, 53);           // 53-bit mantissa
-  const double dm = ldexp(m, 53);                      // the denominator the tests run on
-  const int v = __builtin_ctzll(D);
-  if (v >= 3) return 1;                                // |N| <= 7 has no multiple of 2^v: no candidate
-  const uint64_t Dp = D >> v;
-  if (Dp == 1) return 1;                               // a power of two
-  int ok = 1;
-  for (int t = 0; t < 2; ++t) {
-    const int sh = 53 + t;
-    for (int N = -nmax; N <= nmax; ++N) {
-      if (N == 0 || (N % (1 << v)) != 0) continue;
-      const int64_t Np = N / (1 << v);
-      uint64_t x = (uint64_t)(((Np % (int64_t)Dp) + (int64_t)Dp) % (int64_t)Dp);
-      for (int k = 0; k < sh - v; ++k) x = (x & 1) ? (x + Dp) / 2 : x / 2;  // Np 2^-(sh-v) mod Dp
-      const uint64_t lo = t == 0 ? D : (1ull << 52), hi = t == 0 ? (1ull << 53) : D;
-      const uint64_t k0 = lo > x ? (lo - x + Dp - 1) / Dp : 0;
-      for (uint64_t A = x + k0 * Dp; A < hi; A += Dp) {
-        const __int128 nn = (__int128)((unsigned __int128)A << sh) - N;
-        if (nn % (__int128)D != 0 || ((nn / (__int128)D) & 1) == 0) continue;
-        const double a = (double)A;
-        if (ncand) ++*ncand;
-        if (cand) cand->push_back(a);
-        if (!test(a, dm)) ok = 0;  // (keeps enumerating: cand / ncand are the whole set)
-      }
-    }
-  }
-  return ok;
-}
-int div3_proof(double d, std::vector<double> *cand, long long *ncand) {
-  return div_candidates_pass(
-      d, 6,
-      [](double a, double dm) {
-        const double y = 1.0 / dm;
-        return div3_host(a, dm, y) == a / dm && div3_host(-a, dm, y) == -a / dm;
-      },
-      cand, ncand);
-}
-
-// ---- the 2-instruction exact quotient by a static denominator, and its proof per denominator.
-//   yh = RN(1/d);  yl = RN(e / d) with e = 1 - d yh (exact in one fma, |e| <= u = 2^-53);
-//   u1 = RN(a yl);  q = RN(a yh + u1) (one fma)
-// (common.hip.h: recip_lo_div, div_by_recip2x).  With yl = (e/d)(1 + d1) and u1 = a yl (1 + d2),
-// |d1|, |d2| <= u, and yh = (1 - e)/d, the last fma rounds
-//   s = a yh + u1 = x (1 - e) + x e (1 + d1)(1 + d2) = x (1 + eta),  x = a/d,
-//   eta = e (d1 + d2 + d1 d2),  |eta| <= u^2 (2 + u) < 2.01 * 2^-106.
-// x has a mantissa below 2^53 ulp, so |s - x| < 2.01 * 2^-53 ulp, and q = RN(s) = RN(x) unless a
-// rounding midpoint lies between x and s.  In div3_proof's terms x - midpoint = N / (2 D) ulp with
-// D < 2^53, i.e. more than |N| 2^-54 ulp: only numerators with |N| <= 4 can fail (|N| 2^-54 <
-// 2.01 * 2^-53), none at all when D has three or more trailing zero bits.  div2_proof enumerates
-// them with div3_proof's enumeration and runs the very sequence on each, both signs.  Unlike the
-// 3-instruction form this one DOES fail for some denominators (about 1 % of uniform mantissas:
-// there is no correction step, so a quotient 1 / (2 D) ulp off a midpoint on the wrong side of s
-// stays wrong); those keep the 3-instruction form.  The verdict holds for the yh and yl formed
-// here: the host's IEEE quotients, which the device must reproduce bit for bit (pm_recip2_check).
-static double div2_host(double a, double yh, double yl) {
-  const double u1 = a * yl;
-  return __builtin_fma(a, yh, u1);
-}
-int div2_proof(double d, std::vector<double> *cand, long long *ncand) {
-  return div_candidates_pass(
-      d, 4,
-      [](double a, double dm) {
-        const double yh = 1.0 / dm;
-        const double yl = __builtin_fma(-dm, yh, 1.0) / dm;
-        return div2_host(a, yh, yl) == a / dm && div2_host(-a, yh, yl) == -a / dm;
-      },
-      cand, ncand);
 }
 
 }  // namespace pm
@@ -985,40 +800,19 @@ int pm_comm_barrier(pm_comm_t comm, pm_stream_t stream) {
   return PM_OK;
 }
 
-int pm_selftest_fastdiv(uint64_t seed, int32_t blocks, int32_t per_thread, int32_t emax,
-                        uint64_t *tested, uint64_t *mismatches) {
-  PM_REQUIRE(tested && mismatches, "NULL output");
-  PM_REQUIRE(blocks > 0 && per_thread > 0 && emax >= 0 && emax <= 400, "bad sizes");
-  unsigned long long *d = nullptr;
-  PM_HIP(hipMalloc((void **)&d, sizeof(unsigned long long)));
-  hipStream_t st = resolve_stream(nullptr);
-  PM_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_selftest_fastdiv, dim3(blocks), dim3(256), 0, st,
-                     (unsigned long long)seed, per_thread, emax, d);
-  PM_HIP(hipGetLastError());
-  unsigned long long h = 0;
-  PM_HIP(hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, st));
-  PM_HIP(hipStreamSynchronize(st));
-  PM_HIP(hipFree(d));
-  *mismatches = h;
-  *tested = 4ull * (unsigned long long)per_thread * 256ull * (unsigned long long)blocks;
-  return PM_OK;
-}
-
 int pm_selftest_so_scans(int32_t nhas, uint64_t seed, double *max_rel3, int32_t *sum_mismatches) {
   PM_REQUIRE(max_rel3 && sum_mismatches, "NULL output");
   PM_REQUIRE(nhas >= 1 && nhas <= 64, "nhas must be in [1,64]");
-  double *d = nullptr;
-  PM_HIP(hipMalloc((void **)&d, 4 * sizeof(double)));
+  DeviceScratch<double> d;
+  if (const int rc = d.alloc(4)) return rc;
   hipStream_t st = resolve_stream(nullptr);
-  PM_HIP(hipMemsetAsync(d, 0, 4 * sizeof(double), st));
+  PM_HIP(hipMemsetAsync(d.p, 0, 4 * sizeof(double), st));
   hipLaunchKernelGGL(k_selftest_so_scans, dim3(1), dim3(64), 0, st, (int)nhas,
-                     (unsigned long long)seed, d, reinterpret_cast<int *>(d + 3));
+                     (unsigned long long)seed, d.p, reinterpret_cast<int *>(d.p + 3));
   PM_HIP(hipGetLastError());
   double h[4];
-  PM_HIP(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st));
+  PM_HIP(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, st));
   PM_HIP(hipStreamSynchronize(st));
-  PM_HIP(hipFree(d));
   for (int k = 0; k < 3; ++k) max_rel3[k] = h[k];
   int32_t bad;
   memcpy(&bad, &h[3], sizeof(bad));
@@ -1028,217 +822,14 @@ int pm_selftest_so_scans(int32_t nhas, uint64_t seed, double *max_rel3, int32_t 
 
 int pm_selftest_lane_shift(int32_t *mismatches) {
   PM_REQUIRE(mismatches, "mismatches is NULL");
-  int *d = nullptr;
-  PM_HIP(hipMalloc((void **)&d, sizeof(int)));
+  DeviceScratch<int> d;
+  if (const int rc = d.alloc(1)) return rc;
   hipStream_t st = resolve_stream(nullptr);
-  PM_HIP(hipMemsetAsync(d, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_selftest_lane_shift, dim3(8), dim3(256), 0, st, d);
+  PM_HIP(hipMemsetAsync(d.p, 0, sizeof(int), st));
+  hipLaunchKernelGGL(k_selftest_lane_shift, dim3(8), dim3(256), 0, st, d.p);
   PM_HIP(hipGetLastError());
-  PM_HIP(hipMemcpyAsync(mismatches, d, sizeof(int), hipMemcpyDeviceToHost, st));
+  PM_HIP(hipMemcpyAsync(mismatches, d.p, sizeof(int), hipMemcpyDeviceToHost, st));
   PM_HIP(hipStreamSynchronize(st));
-  PM_HIP(hipFree(d));
-  return PM_OK;
-}
-
-int pm_div3_proven(const double *d, int64_t n, int32_t *proven, int64_t *candidates) {
-  PM_REQUIRE(proven, "proven is NULL");
-  PM_REQUIRE(n == 0 || d, "d is NULL");
-  long long nc = 0;
-  int ok = 1;
-  for (int64_t i = 0; i < n && ok; ++i) ok = div3_proof(d[i], nullptr, &nc);
-  *proven = ok;
-  if (candidates) *candidates = nc;
-  return PM_OK;
-}
-
-int pm_recip_check(const double *d, int64_t n, int32_t *ok) {
-  PM_REQUIRE(ok, "ok is NULL");
-  PM_REQUIRE(n == 0 || d, "d is NULL");
-  *ok = 1;
-  if (n == 0) return PM_OK;
-  double *dd = nullptr, *dy = nullptr;
-  PM_HIP(hipMalloc((void **)&dd, (size_t)n * sizeof(double)));
-  PM_HIP(hipMalloc((void **)&dy, (size_t)n * sizeof(double)));
-  hipStream_t s = resolve_stream(nullptr);
-  PM_HIP(hipMemcpyAsync(dd, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_recip, dim3(256), dim3(256), 0, s, dd, (size_t)n, dy);
-  PM_HIP(hipGetLastError());
-  std::vector<double> y((size_t)n);
-  PM_HIP(hipMemcpyAsync(y.data(), dy, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-  PM_HIP(hipStreamSynchronize(s));
-  PM_HIP(hipFree(dd));
-  PM_HIP(hipFree(dy));
-  for (int64_t i = 0; i < n; ++i) {
-    const double h = 1.0 / d[i];  // the host's correctly rounded quotient
-    if (memcmp(&h, &y[(size_t)i], sizeof(double)) != 0) *ok = 0;
-  }
-  return PM_OK;
-}
-
-int pm_div2_proven(const double *d, int64_t n, int32_t *proven, int64_t *candidates) {
-  PM_REQUIRE(n == 0 || (d && proven), "d or proven is NULL");
-  long long nc = 0;
-  for (int64_t i = 0; i < n; ++i) proven[i] = div2_proof(d[i], nullptr, &nc);
-  if (candidates) *candidates = nc;
-  return PM_OK;
-}
-
-int pm_recip2_check(const double *d, int64_t n, int32_t *ok) {
-  PM_REQUIRE(n == 0 || (d && ok), "d or ok is NULL");
-  if (n == 0) return PM_OK;
-  double *dd = nullptr, *dy = nullptr;
-  PM_HIP(hipMalloc((void **)&dd, (size_t)n * sizeof(double)));
-  PM_HIP(hipMalloc((void **)&dy, 2 * (size_t)n * sizeof(double)));
-  hipStream_t s = resolve_stream(nullptr);
-  PM_HIP(hipMemcpyAsync(dd, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_recip2, dim3(256), dim3(256), 0, s, dd, (size_t)n, dy, dy + n);
-  PM_HIP(hipGetLastError());
-  std::vector<double> y(2 * (size_t)n);
-  PM_HIP(hipMemcpyAsync(y.data(), dy, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-  PM_HIP(hipStreamSynchronize(s));
-  PM_HIP(hipFree(dd));
-  PM_HIP(hipFree(dy));
-  for (int64_t i = 0; i < n; ++i) {
-    const double yh = 1.0 / d[i];  // the host's correctly rounded quotients: div2_proof's pair
-    const double yl = __builtin_fma(-d[i], yh, 1.0) / d[i];
-    ok[i] = memcmp(&yh, &y[(size_t)i], sizeof(double)) == 0 &&
-            memcmp(&yl, &y[(size_t)(n + i)], sizeof(double)) == 0;
-  }
-  return PM_OK;
-}
-
-int pm_selftest_div2(uint64_t seed, int32_t ndenoms, uint64_t *tested, uint64_t *mismatches,
-                     uint64_t *unproven, uint64_t *unproven_mismatches) {
-  PM_REQUIRE(tested && mismatches && unproven && unproven_mismatches, "NULL output");
-  PM_REQUIRE(ndenoms >= 1 && ndenoms <= (1 << 22), "ndenoms must be in [1, 2^22]");
-  std::vector<double> ha, hd, c;
-  std::vector<char> hp;  // the pair's denominator passed the host proof
-  unsigned long long st = seed ? seed : 1, nun = 0;
-  auto next = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return st; };
-  for (int i = 0; i < ndenoms; ++i) {
-    // mantissas as in pm_selftest_div3: uniform, a few units in the last place off 1 or 2, or with
-    // one or two trailing zero bits
-    const unsigned long long r = next();
-    uint64_t D = (1ull << 52) | (next() >> 12);
-    const int kind = (int)(r & 7);
-    if (kind == 0) D = (1ull << 52) + 1 + (next() & 1023);
-    if (kind == 1) D = (1ull << 53) - 1 - (next() & 1023);
-    if (kind == 2) D &= ~1ull;
-    if (kind == 3) D &= ~3ull;
-    const double d = ldexp((double)D, -52 + (int)((r >> 8) % 41) - 20);
-    c.clear();
-    long long nc = 0;
-    const int ok = div2_proof(d, &c, &nc);
-    if (!ok) ++nun;
-    const double scale = ldexp(1.0, (int)((r >> 16) % 41) - 20);
-    for (double a : c) {
-      for (int sgn = 0; sgn < 2; ++sgn) {
-        ha.push_back((sgn ? -a : a) * scale);
-        hd.push_back(d);
-        hp.push_back((char)ok);
-      }
-    }
-    if (ok) {  // and two arbitrary numerators
-      for (int k = 0; k < 2; ++k) {
-        ha.push_back(ldexp((double)((1ull << 52) | (next() >> 12)), -40 - (int)(next() % 30)));
-        hd.push_back(d);
-        hp.push_back(1);
-      }
-    }
-  }
-  const size_t n = ha.size();
-  double *da = nullptr, *dd = nullptr, *dq = nullptr;
-  PM_HIP(hipMalloc((void **)&da, n * sizeof(double)));
-  PM_HIP(hipMalloc((void **)&dd, n * sizeof(double)));
-  PM_HIP(hipMalloc((void **)&dq, n * sizeof(double)));
-  hipStream_t s = resolve_stream(nullptr);
-  PM_HIP(hipMemcpyAsync(da, ha.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
-  PM_HIP(hipMemcpyAsync(dd, hd.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_selftest_div2, dim3(256), dim3(256), 0, s, da, dd, n, dq);
-  PM_HIP(hipGetLastError());
-  std::vector<double> hq(n);
-  PM_HIP(hipMemcpyAsync(hq.data(), dq, n * sizeof(double), hipMemcpyDeviceToHost, s));
-  PM_HIP(hipStreamSynchronize(s));
-  PM_HIP(hipFree(da));
-  PM_HIP(hipFree(dd));
-  PM_HIP(hipFree(dq));
-  unsigned long long bad = 0, ubad = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const double q = ha[i] / hd[i];  // the host's IEEE quotient: the reference
-    if (memcmp(&q, &hq[i], sizeof(double)) != 0) ++(hp[i] ? bad : ubad);
-  }
-  *tested = n;
-  *mismatches = bad;
-  *unproven = nun;
-  *unproven_mismatches = ubad;
-  return PM_OK;
-}
-
-int pm_selftest_div3(uint64_t seed, int32_t ndenoms, uint64_t *tested, uint64_t *mismatches,
-                     uint64_t *unproven, uint64_t *device_div_off, double *one_bad_pair) {
-  PM_REQUIRE(tested && mismatches && unproven && device_div_off, "NULL output");
-  PM_REQUIRE(ndenoms >= 1 && ndenoms <= (1 << 22), "ndenoms must be in [1, 2^22]");
-  std::vector<double> ha, hd, c;
-  unsigned long long st = seed ? seed : 1, nun = 0;
-  auto next = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return st; };
-  for (int i = 0; i < ndenoms; ++i) {
-    // mantissas: uniform, or a few units in the last place off 1 or 2 (where the first product
-    // is worst), or with one or two trailing zero bits
-    const unsigned long long r = next();
-    uint64_t D = (1ull << 52) | (next() >> 12);
-    const int kind = (int)(r & 7);
-    if (kind == 0) D = (1ull << 52) + 1 + (next() & 1023);
-    if (kind == 1) D = (1ull << 53) - 1 - (next() & 1023);
-    if (kind == 2) D &= ~1ull;
-    if (kind == 3) D &= ~3ull;
-    const double d = ldexp((double)D, -52 + (int)((r >> 8) % 41) - 20);
-    c.clear();
-    long long nc = 0;
-    if (!div3_proof(d, &c, &nc)) ++nun;
-    const double scale = ldexp(1.0, (int)((r >> 16) % 41) - 20);
-    for (double a : c) {
-      ha.push_back(a * scale);
-      hd.push_back(d);
-      ha.push_back(-a * scale);
-      hd.push_back(d);
-    }
-    for (int k = 0; k < 2; ++k) {  // and two arbitrary numerators
-      ha.push_back(ldexp((double)((1ull << 52) | (next() >> 12)), -40 - (int)(next() % 30)));
-      hd.push_back(d);
-    }
-  }
-  const size_t n = ha.size();
-  double *da = nullptr, *dd = nullptr, *dq = nullptr;
-  PM_HIP(hipMalloc((void **)&da, n * sizeof(double)));
-  PM_HIP(hipMalloc((void **)&dd, n * sizeof(double)));
-  PM_HIP(hipMalloc((void **)&dq, 2 * n * sizeof(double)));
-  hipStream_t s = resolve_stream(nullptr);
-  PM_HIP(hipMemcpyAsync(da, ha.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
-  PM_HIP(hipMemcpyAsync(dd, hd.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_selftest_div3, dim3(256), dim3(256), 0, s, da, dd, n, dq, dq + n);
-  PM_HIP(hipGetLastError());
-  std::vector<double> hq(2 * n);
-  PM_HIP(hipMemcpyAsync(hq.data(), dq, 2 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  PM_HIP(hipStreamSynchronize(s));
-  PM_HIP(hipFree(da));
-  PM_HIP(hipFree(dd));
-  PM_HIP(hipFree(dq));
-  unsigned long long bad = 0, off = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const double q = ha[i] / hd[i];  // the host's IEEE quotient: the reference
-    if (memcmp(&q, &hq[i], sizeof(double)) != 0) {
-      if (one_bad_pair && !bad) {
-        one_bad_pair[0] = ha[i];
-        one_bad_pair[1] = hd[i];
-      }
-      ++bad;
-    }
-    if (memcmp(&q, &hq[n + i], sizeof(double)) != 0) ++off;
-  }
-  *tested = n;
-  *mismatches = bad;
-  *unproven = nun;
-  *device_div_off = off;
   return PM_OK;
 }
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .columns import ColumnBatch, _HINT_DIV3_OFF, device_reciprocals_exact, div3_proven
+from .columns import ColumnBatch, _HINT_DIV3_OFF, div3_licensed
 from .device import DeviceArray, Event, Graph, Stream, _sh, launch_span
 from .equilibrium import ColumnEquiBatch
 from .psi_so import PsiSOBatch
@@ -611,7 +611,7 @@ class JN2018Ensemble(CoupledEnsemble):
       self._div3_ok = bool(self.cols.uniform_area and self.cols.div3_proven and
                            not (self.cols.__dict__.get("_hints_off", 0) & _HINT_DIV3_OFF) and
                            ((a >= 2.0**-200) & (a <= 2.0**200)).all() and
-                           div3_proven(den) and device_reciprocals_exact(den))
+                           div3_licensed(den))
     return self._div3_ok
 
   def _jn_descriptor(self):

@@ -1,54 +1,14 @@
-"""pm_div2_proven (the host proof behind PM_COLS_DIV2_GRID / PM_COL_DIV2_AREA) against a pure-Python
-restatement in exact rationals: the same candidate numerators and the same verdict per denominator."""
+"""pm_div3_proven and pm_div2_proven (the host proofs behind PM_COLS_DIV3_PROVEN and PM_COLS_DIV2_GRID /
+PM_COL_DIV2_AREA) against a pure-Python restatement in exact rationals (tests/div_proof_reference.py):
+the same candidate numerators and the same verdict per denominator."""
 import ctypes as C
-import math
-from fractions import Fraction as F
 
 import numpy as np
 
+from div_proof_reference import div2_reference, div3_reference
 from pymoc_amd import configs
 from pymoc_amd._lib import check, lib
-
-
-def _fl(x):
-  return float(x)  # (int / int true division rounds a Fraction correctly)
-
-
-def _div2_reference(d):
-  """The candidate numerator mantissas of d (quotient within 4 / (2 D) ulp of a rounding midpoint)
-  and whether  yh = RN(1/d); yl = RN((1 - d yh) / d); q = RN(a yh + RN(a yl))  is the correctly
-  rounded quotient on every one of them, both signs."""
-  m, _ = math.frexp(abs(d))
-  D = int(m * 2**53)
-  dm = float(D)
-  v = (D & -D).bit_length() - 1
-  Dp = D >> v
-  cands = set()
-  if v < 3 and Dp > 1:
-    for t in (0, 1):
-      sh = 53 + t
-      for N in range(-4, 5):
-        if N == 0 or N % (1 << v):
-          continue
-        A0 = ((N >> v) * pow((1 << (sh - v)) % Dp, -1, Dp)) % Dp
-        lo, hi = (D, 1 << 53) if t == 0 else (1 << 52, D)
-        A = A0 + ((lo - A0 + Dp - 1) // Dp) * Dp
-        while A < hi:
-          q, r = divmod(A * (1 << sh) - N, D)
-          if r == 0 and q % 2 == 1:
-            cands.add(A)
-          A += Dp
-  yh = _fl(F(1) / F(dm))
-  e = F(1) - F(dm) * F(yh)
-  assert _fl(e) == e  # the residual of the reciprocal is exact in one fma
-  yl = _fl(e / F(dm))
-  ok = True
-  for A in cands:
-    for a in (float(A), -float(A)):
-      u = _fl(F(a) * F(yl))
-      if _fl(F(a) * F(yh) + F(u)) != _fl(F(a) / F(dm)):
-        ok = False
-  return ok, len(cands)
+from pymoc_amd.columns import div3_proven
 
 
 def _library(d):
@@ -78,7 +38,7 @@ def test_div2_proof_matches_its_restatement():
   for name, ds in (("grid", grid), ("areas", areas), ("random", rnd), ("edge", edge)):
     fails[name] = 0
     for d in ds:
-      got, ref = _library(d), _div2_reference(float(d))
+      got, ref = _library(d), div2_reference(float(d))
       assert got == ref, (name, float(d).hex(), got, ref)
       fails[name] += not got[0]
       if name == "grid":
@@ -100,3 +60,29 @@ def test_div2_proof_rejects_what_it_cannot_scale():
   arr = np.array([1.5, 0.0, 40.0])
   check(lib.pm_div2_proven(arr.ctypes.data, 3, ok.ctypes.data, None))
   assert list(ok) == [1, 0, 1]
+
+
+def test_div3_proof_matches_its_restatement():
+  """pm_div3_proven (host function behind PM_COLS_DIV3_PROVEN): the same candidate numerators and
+  the same verdict as an exact-rational restatement, for uniform mantissas, mantissas next to 1 and
+  2, mantissas with trailing zeros and the grid spacings of BASELINE's grids; zero, subnormal and
+  non-finite denominators are not proven."""
+  rng = np.random.default_rng(5)
+  ds = list(rng.uniform(1, 2, 150) * 2.0**rng.integers(-30, 30, 150))
+  ds += [1.0 + k * 2.0**-52 for k in range(1, 40)] + [2.0 - k * 2.0**-52 for k in range(1, 40)]
+  ds += [float((np.float64(x).view(np.uint64) & ~np.uint64(1)).view(np.float64)) for x in rng.uniform(1, 2, 40)]
+  ds += [float((np.float64(x).view(np.uint64) & ~np.uint64(3)).view(np.float64)) for x in rng.uniform(1, 2, 40)]
+  ds += [3.0, 6e13, 1e-7, 40.0, 0.1, 86400.0 * 30]
+  for mk in (configs.config2, configs.config5):
+    ds += _grid_denominators(mk(N=2)["z"])
+  for d in ds:
+    d = float(d)
+    ok, nc = C.c_int32(-1), C.c_int64(-1)
+    arr = np.array([d])
+    check(lib.pm_div3_proven(arr.ctypes.data, 1, C.byref(ok), C.byref(nc)))
+    rok, rnc = div3_reference(d)
+    assert (bool(ok.value), nc.value) == (rok, rnc), (d, ok.value, nc.value, rok, rnc)
+    assert ok.value == 1  # (no denominator is known to fail; the kernels still ask for the proof)
+  for bad in (0.0, -0.0, np.inf, -np.inf, np.nan, 5e-324, 2.0**-1060):
+    assert not div3_proven([1.5, bad])
+  assert div3_proven([]) and div3_proven([1.5, -3.0, 2.0**-1000, 2.0**1000])

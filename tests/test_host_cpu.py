@@ -697,77 +697,3 @@ def test_brentq_restatement_equals_scipy():
   assert seen > 200
   with pytest.raises(ValueError):
     brentq(lambda y: 1. + y * y, -1., 1.)
-
-
-def _div3_reference(d):
-  """Pure-Python restatement of pm_div3_proven for one denominator (exact rationals): the
-  candidate numerators (quotient within 6 / (2 D) ulp of a rounding midpoint) and whether the
-  3-instruction quotient is correctly rounded on every one of them."""
-  import math
-  from fractions import Fraction as F
-
-  def fma(a, b, c):
-    return float(F(a) * F(b) + F(c))  # (int / int true division rounds correctly)
-
-  m, _ = math.frexp(abs(d))
-  D = int(m * 2**53)
-  dm = float(D)
-  y = 1.0 / dm
-  v = (D & -D).bit_length() - 1
-  Dp = D >> v
-  cands = set()
-  if v < 3 and Dp > 1:
-    for t in (0, 1):
-      sh = 53 + t
-      for N in range(-6, 7):
-        if N == 0 or N % (1 << v):
-          continue
-        A0 = ((N >> v) * pow((1 << (sh - v)) % Dp, -1, Dp)) % Dp
-        lo, hi = (D, 1 << 53) if t == 0 else (1 << 52, D)
-        A = A0 + ((lo - A0 + Dp - 1) // Dp) * Dp
-        while A < hi:
-          q, r = divmod(A * (1 << sh) - N, D)
-          if r == 0 and q % 2 == 1:
-            cands.add(A)
-          A += Dp
-  ok = True
-  for A in cands:
-    for a in (float(A), -float(A)):
-      q0 = float(F(a) * F(y))
-      r = fma(-dm, q0, a)
-      if fma(r, y, q0) != float(F(a) / F(dm)):
-        ok = False
-  return ok, len(cands)
-
-
-def test_div3_proof_matches_its_restatement():
-  """pm_div3_proven (host function behind PM_COLS_DIV3_PROVEN): the same candidate numerators and
-  the same verdict as an exact-rational restatement, for uniform mantissas, mantissas next to 1 and
-  2, mantissas with trailing zeros and the grid spacings of BASELINE's grids; zero, subnormal and
-  non-finite denominators are not proven."""
-  import ctypes as C
-  from pymoc_amd._lib import lib, check
-  from pymoc_amd.columns import div3_proven
-  from pymoc_amd import configs
-  rng = np.random.default_rng(5)
-  ds = list(rng.uniform(1, 2, 150) * 2.0**rng.integers(-30, 30, 150))
-  ds += [1.0 + k * 2.0**-52 for k in range(1, 40)] + [2.0 - k * 2.0**-52 for k in range(1, 40)]
-  ds += [float(np.float64(x).view(np.uint64) & ~np.uint64(3)) for x in []]
-  ds += [float((np.float64(x).view(np.uint64) & ~np.uint64(1)).view(np.float64)) for x in rng.uniform(1, 2, 40)]
-  ds += [float((np.float64(x).view(np.uint64) & ~np.uint64(3)).view(np.float64)) for x in rng.uniform(1, 2, 40)]
-  ds += [3.0, 6e13, 1e-7, 40.0, 0.1, 86400.0 * 30]
-  for mk in (configs.config2, configs.config5):
-    z = mk(N=2)["z"]
-    dz = np.diff(z)
-    ds += list(np.unique(dz)) + list(np.unique(0.5 * (dz[1:] + dz[:-1])))
-  for d in ds:
-    d = float(d)
-    ok, nc = C.c_int32(-1), C.c_int64(-1)
-    arr = np.array([d])
-    check(lib.pm_div3_proven(arr.ctypes.data, 1, C.byref(ok), C.byref(nc)))
-    rok, rnc = _div3_reference(d)
-    assert (bool(ok.value), nc.value) == (rok, rnc), (d, ok.value, nc.value, rok, rnc)
-    assert ok.value == 1  # (no denominator is known to fail; the kernels still ask for the proof)
-  for bad in (0.0, -0.0, np.inf, -np.inf, np.nan, 5e-324, 2.0**-1060):
-    assert not div3_proven([1.5, bad])
-  assert div3_proven([]) and div3_proven([1.5, -3.0, 2.0**-1000, 2.0**1000])
