@@ -982,6 +982,40 @@ struct pm_steady_check {
 /* the struct is named by its tag only: a typedef of the same name would clash with the function */
 int pm_steady_check(const struct pm_steady_check *c, pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Time-dependent forcing of an ensemble (pymoc_amd.ForcingSchedule), ONE launch: a piecewise-
+ * linear schedule evaluated at time t and written into up to 8 target arrays that the stepping
+ * kernels re-read at every launch (the columns' bs, the channel's tau, bs_SO, b_rest, surflux).
+ * (no counterpart: the user loop's assignments `basin.bs = ...`, `PsiSO.tau = ...` ahead of a
+ * step.)
+ *   knots   [K] HOST array, strictly increasing and finite, shared by all members and targets:
+ *           the bracket of t depends on t alone, so the entry finds it here, once, and the kernel
+ *           receives it as arguments;
+ *   target  rows [row0, row0 + n) of a dense array of rows of `len` doubles at `dst` (`bs_north`
+ *           is rows [n, 2n) of the columns' bs with len = 1); `values` holds the knot values,
+ *           knot axis first: [K][len] shared by all members (per_member = 0) or [K][n][len]
+ *           (per_member = 1: one knot's slab is the target's own layout, so its loads coalesce
+ *           across members and levels exactly as the stores do).
+ * Every written element equals np.interp(t, knots, values of that element) BIT FOR BIT: values
+ * held outside the knots, the value itself on a knot, K = 1, slope = (f1 - f0) / (x1 - x0) then
+ * slope * (t - x0) + f0 uncontracted, np.interp's fallbacks when that is NaN; t = NaN writes NaN
+ * (with K = 1 the knot's value, as np.interp does).
+ * Nothing outside the n rows of a target is touched.
+ * Sizes: n >= 1, K >= 1, 1 <= ntargets <= 8, every len >= 1 and row0 >= 0, no NULL pointer.     */
+#define PM_FORCING_MAX_TARGETS 8
+typedef struct pm_forcing_target {
+  double *dst; int64_t row0;             /* rows [row0, row0 + n) of [.][len] are written         */
+  const double *values;                  /* device: [K][len] or [K][n][len]                       */
+  int32_t len, per_member;
+} pm_forcing_target;
+struct pm_forcing {
+  int32_t n, K, ntargets, reserved;
+  const double *knots;                   /* HOST [K]                                              */
+  pm_forcing_target target[PM_FORCING_MAX_TARGETS];
+};
+/* the struct is named by its tag only, as pm_steady_check's is */
+int pm_forcing_apply(const struct pm_forcing *f, double t, pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

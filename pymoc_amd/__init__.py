@@ -23,6 +23,7 @@ from . import configs
 from . import sharding
 from .ensembles import (EquiIterationEnsemble, ColumnThermwindEnsemble, TwoColEnsemble, JN2018Ensemble,
                         TwoBasinEnsemble)
+from .forcing import ForcingSchedule
 from . import diagnostics
 from . import plotting
 from . import steady

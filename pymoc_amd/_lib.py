@@ -259,6 +259,22 @@ class pm_steady_check(C.Structure):
   ]
 
 
+PM_FORCING_MAX_TARGETS = 8
+
+
+class pm_forcing_target(C.Structure):
+  """Mirror of `struct pm_forcing_target` (include/pymoc_hip.h)."""
+  _fields_ = [("dst", c_dp), ("row0", C.c_int64), ("values", c_dp), ("len", C.c_int32),
+              ("per_member", C.c_int32)]
+
+
+class pm_forcing(C.Structure):
+  """Mirror of `struct pm_forcing` (include/pymoc_hip.h); `knots` is a HOST address."""
+  _fields_ = [("n", C.c_int32), ("K", C.c_int32), ("ntargets", C.c_int32),
+              ("reserved", C.c_int32), ("knots", C.c_void_p),
+              ("target", pm_forcing_target * PM_FORCING_MAX_TARGETS)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -356,6 +372,7 @@ SIGNATURES = {
     "pm_twobasin_overturning_sections": (C.c_int, [C.POINTER(pm_twobasin_overturning),
                                                    C.c_void_p]),
     "pm_steady_check": (C.c_int, [C.POINTER(pm_steady_check), C.c_void_p]),
+    "pm_forcing_apply": (C.c_int, [C.POINTER(pm_forcing), C.c_double, C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -158,11 +158,18 @@ class CoupledEnsemble(object):
                    member, repeated along the axis -- unless n equals the axis length, when it is
                    the shared profile; a scalar or any other 1-D array is shared
     ("2d", axis)   a profile on cfg[axis]: 2-D is per member, anything else is shared
-  None: the driver's constructor reads its cfg by itself and cannot be restarted on a subset."""
+  None: the driver's constructor reads its cfg by itself and cannot be restarted on a subset.
+
+  FORCING_TARGETS is the single statement of what a `forcing=ForcingSchedule(...)` may set:
+    name -> (the device array, as an attribute path from the driver; the group of n rows its
+             first row starts; the row length: None = one value per member, "y" = a profile on
+             cfg['y'], "tau" = whichever of the two the batch's tau is)
+  None: the driver takes no schedule."""
 
   NGROUPS = 2
   FIELDS = ("b_basin", "b_north", "Psi", "Psi_SO")
   MEMBER_KEYS = None
+  FORCING_TARGETS = None
   RESTART_PHASE = None  # the steps s = RESTART_PHASE (mod MOC_up_iters) can be restarted from
 
   @classmethod
@@ -203,6 +210,73 @@ class CoupledEnsemble(object):
       if key in cfg and cls._rule(cfg, key, n)[2]:
         out[key] = cls.read(cfg, key, n)[keep]
     return out
+
+  @classmethod
+  def _has_channel(cls, cfg):
+    return 'y' in cfg
+
+  @classmethod
+  def forcing_lengths(cls, cfg, n):
+    """name -> row length of the targets a schedule may name for this cfg (host only)."""
+    out = {}
+    for name, (_, _, axis) in cls.FORCING_TARGETS.items():
+      if axis is None:
+        out[name] = 1
+      elif cls._has_channel(cfg):
+        profile = axis == "y" or cls.read(cfg, 'tau', n).ndim == 2
+        out[name] = np.asarray(cfg['y']).size if profile else 1
+    return out
+
+  def _check_forcing(self, forcing, cfg, n, **excluded):
+    """A constructor's first act, before any device state: refuse what a schedule cannot go with,
+    and the schedule's names and shapes against this cfg."""
+    self._forcing, self._forced_at = None, -1
+    if forcing is None:
+      return
+    for kw, on in excluded.items():
+      if on:
+        raise ValueError("forcing does not go with %s=True: a captured or persistent launch "
+                         "spans the steps the schedule is applied at" % kw)
+    forcing.check(self.forcing_lengths(cfg, n), n)
+
+  def _bind_forcing(self, forcing, cfg):
+    """A constructor's last act ahead of its own first update (which uses the cfg's values)."""
+    if forcing is None:
+      return
+    n, lengths = self.n, self.forcing_lengths(cfg, self.n)
+    targets = {}
+    for name in forcing.values:
+      path, group, _ = self.FORCING_TARGETS[name]
+      a = self
+      for attr in path.split("."):
+        a = getattr(a, attr)
+      targets[name] = (a, group * n, lengths[name])
+    self._forcing = forcing.bind(n, targets, stream=self.stream)
+    # PM_COL_STATIC_IN_RANGE was derived from the cfg's bs; it stays only where every value the
+    # schedule can write is zero or inside the exact-division window [2^-200, 2^200]: knots that
+    # are zero or within [2^-100, 2^100] guarantee that (an interpolated value is a rounded sum of
+    # terms no smaller than 2^-153 next to such knots).  Otherwise the columns test every operand
+    # (bit-identical results, include/pymoc_hip.h).
+    bs = [np.abs(forcing.values[k]) for k in ("bs", "bs_north") if k in forcing.values]
+    if any(not ((v == 0) | ((v >= 2.0**-100) & (v <= 2.0**100))).all() for v in bs):
+      self.cols._par_ok["bs"] = np.zeros(self.cols.ncols, dtype=bool)
+      self.cols._upload_flags()
+
+  def _apply_forcing(self):
+    """THE rule of when a schedule is evaluated: at the top of loop iteration s = self.ii, before
+    anything else that iteration does, for s = 0 and every s = RESTART_PHASE (mod MOC_up_iters),
+    at t = s * dt; the values are held until the next such iteration.  Those are exactly the first
+    steps of the launch intervals, so the forcing is constant within a launch, and it is where a
+    reference user loop that assigns at the top of the loop body puts it: ahead of the MOC update
+    of iteration s for JN2018Ensemble, behind the update that follows step s - 1 for
+    TwoColEnsemble."""
+    if self._forcing is None or self._forced_at == self.ii:
+      return
+    s = self.ii
+    if s == 0 or s % self.M == self.RESTART_PHASE % self.M:
+      with launch_span(self.timer, "k_forcing_apply", self.stream):
+        self._forcing.apply(s * self.dt, self.stream)
+      self._forced_at = s
 
   @staticmethod
   def _check_arith(arith):
@@ -295,10 +369,16 @@ class TwoColEnsemble(CoupledEnsemble):
   # after the update that follows step s - 1 (example_twocol.py:85-96): the constructor's own
   # update is the one at a restart
   RESTART_PHASE = 1
+  FORCING_TARGETS = dict(bs=("cols.bs", 0, None), bs_north=("cols.bs", 1, None),
+                         tau=("so.tau", 0, "tau"), bs_SO=("bs_SO", 0, "y"))
+
+  @classmethod
+  def _has_channel(cls, cfg):
+    return 'y' in cfg and 'bs_SO' in cfg
 
   def __init__(self, cfg, stream=None, lanes_per_col=0, comm=None, n_total=None,
                diag_iters=None, keep_history=False, arith="exact", overlap_updates=False,
-               fused_run=None, gather="all", gather_overlap=True):
+               fused_run=None, gather="all", gather_overlap=True, forcing=None):
     """`fused_run`: carry the members through whole stretches of the loop -- many [refresh the
     overturning, MOC_up_iters steps] intervals -- in ONE launch of the persistent per-member
     kernel (pm_twocol_run), ending a launch only where the diagnostics are gathered.  Same device
@@ -316,10 +396,14 @@ class TwoColEnsemble(CoupledEnsemble):
     steps (default cfg['Diag_iters']) and by `gather_diagnostics()` at the end of a run;
     `gather="root"` sends them to rank 0 only, `gather_overlap` runs the exchange on a
     communication stream of its own beside the stepping (sharding.DiagnosticGather).
-    `arith="contracted"`: the columns step in the opt-in tolerance mode (ColumnBatch.steps)."""
+    `arith="contracted"`: the columns step in the opt-in tolerance mode (ColumnBatch.steps).
+    `forcing`: a ForcingSchedule for bs, bs_north and, with an SO channel, tau (in the form of the
+    batch's tau: one value per member or a profile on y) and bs_SO, applied by the rule of
+    `_apply_forcing`; the constructor's own update uses the cfg's values.  Not with fused_run."""
     z = cfg['z']
     nz = z.size
     n = self.members(cfg)
+    self._check_forcing(forcing, cfg, n, fused_run=fused_run)
     rd = lambda key: self.read(cfg, key, n)  # noqa: E731
     self.n, self.nz = n, nz
     self.dt, self.M, self.nb = float(cfg['dt']), int(cfg['MOC_up_iters']), int(cfg['nb'])
@@ -359,6 +443,7 @@ class TwoColEnsemble(CoupledEnsemble):
     self._fused_run = False if fused_run is None else bool(fused_run)
     self.run_status = (DeviceArray.zeros((n,), np.int32, stream=stream) if self._fused_run
                        else None)
+    self._bind_forcing(forcing, cfg)
     self._update()  # AMOC.solve(); AMOC.Psibz() [; SO.solve()] on the initial profiles
 
   def _solve_so(self, stream):
@@ -449,6 +534,7 @@ class TwoColEnsemble(CoupledEnsemble):
       return self._run_fused(nsteps)
     remaining = int(nsteps)
     while remaining > 0:
+      self._apply_forcing()
       n = self._interval(remaining)
       self._steps(n)
       self.ii += n
@@ -486,11 +572,14 @@ class JN2018Ensemble(CoupledEnsemble):
                      bs_SO0=("rows", "y"))
   # after step s's MOC update, before the step (run_JansenNadeau_2018.py:204-217)
   RESTART_PHASE = 0
+  FORCING_TARGETS = dict(bs=("cols.bs", 0, None), bs_north=("cols.bs", 1, None),
+                         tau=("so.tau", 0, "tau"), b_rest=("ml.b_rest", 0, "y"),
+                         surflux=("ml.surflux", 0, "y"))
 
   def __init__(self, cfg, stream=None, lanes_per_col=0, use_graph=False, fused=None,
                comm=None, n_total=None, diag_iters=None, keep_history=False, arith="exact",
                shared_coef=True, fused_run=None, gather="all", gather_overlap=True,
-               split_lanes=False):
+               split_lanes=False, forcing=None):
     """`fused_run`: whole stretches of the loop -- many [PsiSO.solve, AMOC.solve / Psibz,
     MOC_up_iters steps] intervals -- in ONE launch of the persistent per-member kernel
     (pm_jn2018_run), ending a launch only where diagnostics are sampled or gathered;
@@ -505,7 +594,11 @@ class JN2018Ensemble(CoupledEnsemble):
     kind when all members' profiles are identical (checked here on the host arrays;
     PM_JN_SHARED_COEF); results are bit-identical either way.
     `split_lanes`: the fused loop steps both columns of a member together, one per half of the
-    wavefront (PM_JN_SPLIT_LANES; bit-identical; measured a tie on config 5, hence opt-in)."""
+    wavefront (PM_JN_SPLIT_LANES; bit-identical; measured a tie on config 5, hence opt-in).
+    `forcing`: a ForcingSchedule for bs, bs_north, tau (in the form of the batch's tau), b_rest
+    and surflux, applied by the rule of `_apply_forcing` -- ahead of the MOC update of the step,
+    in run() on every path and in moc_update().  Not with use_graph or fused_run."""
+    self._check_forcing(forcing, cfg, self.members(cfg), use_graph=use_graph, fused_run=fused_run)
     self.arith = self._check_arith(arith)
     self.shared_coef = bool(shared_coef)
     self.split_lanes = bool(split_lanes)
@@ -560,6 +653,7 @@ class JN2018Ensemble(CoupledEnsemble):
     self.diag_iters = (cfg.get('Diag_iters', 10 * self.M) if diag_iters is None
                        else diag_iters)
     self._init_gather(comm, n_total, keep_history, gather, gather_overlap)
+    self._bind_forcing(forcing, cfg)
 
   def _after_update(self):
     if self.recorder is not None:
@@ -686,6 +780,7 @@ class JN2018Ensemble(CoupledEnsemble):
       return self._run_fused(nsteps)
     remaining = int(nsteps)
     while remaining > 0 and self._fused:
+      self._apply_forcing()
       if self.ii % self.M == 0 and self._updated_at != self.ii:
         self._update()
         self._after_update()
@@ -704,6 +799,7 @@ class JN2018Ensemble(CoupledEnsemble):
         self.ii += self.M
         remaining -= self.M
         continue
+      self._apply_forcing()
       if self.ii % self.M == 0 and self._updated_at != self.ii:
         self._update()
         self._after_update()
@@ -717,6 +813,7 @@ class JN2018Ensemble(CoupledEnsemble):
     Only at a step the script updates at (ii % MOC_up_iters == 0)."""
     if self.ii % self.M:
       raise ValueError("step %d is not a MOC update step (MOC_up_iters=%d)" % (self.ii, self.M))
+    self._apply_forcing()
     if self._updated_at != self.ii:
       self._update()
       self._after_update()
