@@ -10,6 +10,8 @@ Pinned against the reference's own outputs (tests/golden/equi_column.npz, set G1
 """
 import numpy as np
 from scipy import integrate
+from scipy.integrate import _bvp
+from scipy.sparse.linalg import splu
 
 
 def problem(f=1.2e-4, b_s=0.025, b_bot=None, B_int=3e3, A=7e13, nz=100, H_guess=1500.,
@@ -44,8 +46,8 @@ def _profiles(q):
   return kappa, dkappa, psi
 
 
-def solve(q, tol=1e-3, max_nodes=1000):
-  """-> dict(x, y, H, status, niter, sol): what Equi_Column.solve obtains from solve_bvp."""
+def functions(q):
+  """-> (ode, bc, hfree, has_bbot, bz): the problem closures solve_bvp is handed."""
   f, A = q['f'], q['A']
   kappa, dkappa, psi = _profiles(q)
   bs = -q['b_s'] / f**2
@@ -70,6 +72,12 @@ def solve(q, tol=1e-3, max_nodes=1000):
     r.append(yb[2] - bs / H)
     return np.array(r)
 
+  return ode, bc, hfree, has_bbot, bz
+
+
+def solve(q, tol=1e-3, max_nodes=1000):
+  """-> dict(x, y, H, status, niter, sol): what Equi_Column.solve obtains from solve_bvp."""
+  ode, bc, hfree, has_bbot, bz = functions(q)
   nz = q['nz']
   zi = np.linspace(-1, 0, nz)
   y0 = np.zeros((4, nz))
@@ -80,6 +88,113 @@ def solve(q, tol=1e-3, max_nodes=1000):
   H = res.p[0] if hfree else q['H']
   return dict(x=res.x, y=res.y, yp=res.yp, H=H, status=res.status, niter=res.niter,
               sol=res.sol)
+
+
+def newton_system(q, x):
+  """-> (fun, bc, col_fun, jac, k): solve_bvp's wrapped problem functions and the two callbacks
+  `_bvp.solve_newton` takes on the mesh x (what `_bvp.prepare_sys` builds, on the same blocks:
+  forward-difference Jacobians, `construct_global_jac`)."""
+  ode, bc, hfree = functions(q)[:3]
+  k, m = (1 if hfree else 0), x.size
+  h = np.diff(x)
+  fun, bcw = _bvp.wrap_functions(ode, bc, None, None, k, x[0], None, None, float)[:2]
+  xm = x[:-1] + 0.5 * h
+  i_jac, j_jac = _bvp.compute_jac_indices(4, m, k)
+
+  def col_fun(y, p):
+    return _bvp.collocation_fun(fun, y, p, x, h)
+
+  def jac(y, p, y_middle, f, f_middle, bc0):
+    df_dy, df_dp = _bvp.estimate_fun_jac(fun, x, y, p, f)
+    df_dy_m, df_dp_m = _bvp.estimate_fun_jac(fun, xm, y_middle, p, f_middle)
+    dya, dyb, dp = _bvp.estimate_bc_jac(bcw, y[:, 0], y[:, -1], p, bc0)
+    return _bvp.construct_global_jac(4, m, k, i_jac, j_jac, h, df_dy, df_dy_m, df_dp, df_dp_m,
+                                     dya, dyb, dp)
+
+  return fun, bcw, col_fun, jac, k
+
+
+def _gap(lhs, rhs, scale):
+  """|lhs - rhs| / scale of a comparison `lhs < rhs`; inf where an operand is not finite (a
+  comparison with NaN is false, and one with inf is decided, in any arithmetic)."""
+  with np.errstate(all='ignore'):
+    g = abs(lhs - rhs) / scale
+  return float(g) if np.isfinite(g) else np.inf
+
+
+def newton_pass(q, x, y, p, tol=1e-3):
+  """What solve_bvp does between two mesh changes, from the iterate (y [4, m], p = H or None) on
+  the mesh x: `_bvp.solve_newton` (restated below, _bvp.py:438-499, so that its path can be
+  returned), then the residual estimate and insertion count of solve_bvp's loop (:1086-1104).
+  -> (y, p, singular, yp, rms, nadd, info, rec): p as solve_newton returns it ([H] or []),
+  info = (max rms, max |bc residual|), rec = dict(niter: iterations entered, njev, alphas: the
+  damping factor each iteration ended on, converged: the stopping rule was met, margins:
+  |cost_new - rhs| / cost of every line-search test `cost_new < rhs`, stop_margins: distance from 1
+  of the largest ratio in every stopping test)."""
+  x = np.asarray(x, float)
+  y = np.array(y, float)
+  fun, bc, col_fun, jac, k = newton_system(q, x)
+  p = np.array([p], float) if k else np.array([])
+  m, h = x.size, np.diff(x)
+  tol_r = 2 / 3 * h * 5e-2 * tol
+  max_njev, max_iter, sigma, tau, n_trial = 4, 8, 0.2, 0.5, 4
+  col_res, y_middle, f, f_middle = col_fun(y, p)
+  bc_res = bc(y[:, 0], y[:, -1], p)
+  res = np.hstack((col_res.ravel(order='F'), bc_res))
+  rec = dict(niter=0, njev=0, alphas=[], converged=False, margins=[], stop_margins=[])
+  singular, recompute_jac = False, True
+  for iteration in range(max_iter):
+    rec['niter'] += 1
+    if recompute_jac:
+      J = jac(y, p, y_middle, f, f_middle, bc_res)
+      rec['njev'] += 1
+      try:
+        LU = splu(J)
+      except RuntimeError:
+        singular = True
+        break
+      step = LU.solve(res)
+      cost = np.dot(step, step)
+    y_step = step[:m * 4].reshape((4, m), order='F')
+    p_step = step[m * 4:]
+    alpha = 1
+    for trial in range(n_trial + 1):
+      y_new = y - alpha * y_step
+      p_new = p - alpha * p_step
+      col_res, y_middle, f, f_middle = col_fun(y_new, p_new)
+      bc_res = bc(y_new[:, 0], y_new[:, -1], p_new)
+      res = np.hstack((col_res.ravel(order='F'), bc_res))
+      step_new = LU.solve(res)
+      cost_new = np.dot(step_new, step_new)
+      rec['margins'].append(_gap(cost_new, (1 - 2 * alpha * sigma) * cost, cost))
+      if cost_new < (1 - 2 * alpha * sigma) * cost:
+        break
+      if trial < n_trial:
+        alpha *= tau
+    y, p = y_new, p_new
+    rec['alphas'].append(alpha)
+    if rec['njev'] == max_njev:
+      break
+    with np.errstate(all='ignore'):
+      worst = max(np.max(np.abs(col_res) / (tol_r * (1 + np.abs(f_middle)))),
+                  np.max(np.abs(bc_res)) / tol)
+    rec['stop_margins'].append(_gap(worst, 1.0, 1.0))
+    if (np.all(np.abs(col_res) < tol_r * (1 + np.abs(f_middle))) and
+        np.all(np.abs(bc_res) < tol)):
+      rec['converged'] = True
+      break
+    if alpha == 1:
+      step, cost, recompute_jac = step_new, cost_new, False
+    else:
+      recompute_jac = True
+  col_res, y_middle, f, f_middle = _bvp.collocation_fun(fun, y, p, x, h)
+  bc_res = bc(y[:, 0], y[:, -1], p)
+  sol = _bvp.create_spline(y, f, x, h)
+  rms = _bvp.estimate_rms_residuals(fun, sol, x, h, p, 1.5 * col_res / h, f_middle)
+  with np.errstate(invalid='ignore'):
+    nadd = int(((rms > tol) & (rms < 100 * tol)).sum() + 2 * (rms >= 100 * tol).sum())
+  info = (np.max(rms), np.max(np.abs(bc_res)))
+  return y, p, singular, f, rms, nadd, info, rec
 
 
 def outputs(q, r):
