@@ -229,6 +229,27 @@ int pm_column_steps(const pm_columns *cols, const double *wA, const double *vdx_
                     const double *b_in, double dt, int32_t nsteps, int32_t ops,
                     int32_t lanes_per_col, pm_stream_t stream);
 
+/* Backward-Euler column steps: an EXTENSION with no reference counterpart (the reference's
+ * vertadvdiff, column.py:210-249, is forward Euler and unstable above kappa dt / dz^2 = 1/2), so a
+ * TOLERANCE path: bit-identical to nothing but itself (nsteps = k in one launch equals k launches of
+ * one step, bit for bit).  With the reference's discretisation -- dz = z[1:] - z[:-1],
+ * dzc_i = 0.5 (dz[i] + dz[i-1]), w_i = weff_i / Area_i (weff = wA - d(A kappa)/dz, the upwind test
+ * `w_i < 0` the reference's own) --
+ *   cl_i = (w_i < 0 ? 0 : w_i / dz[i-1]) + kappa_i / (dzc_i dz[i-1])
+ *   cu_i = (w_i < 0 ? -w_i / dz[i] : 0)  + kappa_i / (dzc_i dz[i])
+ * one step is: convect() (PM_OP_CONVECT, columns flagged PM_COL_DO_CONV: the explicit kernel's device
+ * function, same bits); b[nz-1] = bs unless the column is flagged PM_COL_DO_CONV; b[0] = bbot; solve
+ *   (1 + dt (cl_i + cu_i)) x_i - dt cl_i x_{i-1} - dt cu_i x_{i+1} = b_i,   i = 1 .. nz-2
+ * (one strictly diagonally dominant tridiagonal system per column, no pivoting; under PM_COL_BZBOT
+ * x_0 = x_1 - bzbot dz[0] is folded into row 1 and b[0] = x_1 - bzbot dz[0] afterwards); store x.
+ * The matrix is factored once per launch.  Reads pm_columns as pm_column_steps does (ksel / nsel,
+ * per-column flags, nonfinite); the exact-division hints are ignored.  wA [ncols][nz] may be NULL
+ * (= 0).  ops: PM_OP_CONVECT | PM_OP_VERTADVDIFF, optionally PM_OP_WEFF; PM_OP_HORADV,
+ * PM_OP_CONTRACTED, PM_OP_WA_PSI, PM_OP_WA_TWOBASIN, nsteps < 0 and a dt that is not finite and
+ * positive are PM_EINVAL; nsteps == 0 launches nothing.                                          */
+int pm_column_steps_implicit(const pm_columns *cols, const double *wA, double dt, int32_t nsteps,
+                             int32_t ops, pm_stream_t stream);
+
 /* weff[ncols][nz] = wA - d(A kappa)/dz of each column's coefficient set in use (column.py:241),
  * for pm_column_steps(..., ops | PM_OP_WEFF).                                                 */
 int pm_column_weff(const pm_columns *cols, const double *wA, double *weff, pm_stream_t stream);

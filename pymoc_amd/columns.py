@@ -99,6 +99,27 @@ def div2_proven(denominators):
   return proven.astype(bool)
 
 
+SCHEMES = ("explicit", "implicit")
+
+
+def check_scheme(scheme, vdx_in=None, arith="exact", psi_forcing=None, twobasin_forcing=None,
+                 b_in=None, lanes_per_col=0):
+  """ValueError for an unknown column time scheme, or for what the implicit one does not take:
+  horadv (vdx_in / b_in), the contracted arithmetic, forcing formed inside the explicit kernel, a
+  choice of lanes per column (its kernel always gives a column one wavefront)."""
+  if scheme not in SCHEMES:
+    raise ValueError("scheme must be 'explicit' or 'implicit' (got %r)" % (scheme,))
+  if scheme == "implicit":
+    if vdx_in is not None or b_in is not None:
+      raise ValueError("scheme='implicit' has no horadv (vdx_in / b_in)")
+    if lanes_per_col:
+      raise ValueError("scheme='implicit' takes no lanes_per_col: one wavefront per column")
+    if arith == "contracted":
+      raise ValueError("scheme='implicit' excludes arith='contracted'")
+    if psi_forcing is not None or twobasin_forcing is not None:
+      raise ValueError("scheme='implicit' takes wA as an array (no psi_forcing / twobasin_forcing)")
+
+
 class ColumnBatch(object):
   def __init__(self, z, kappa, area, b, bs=0.025, bbot=0.0, bzbot=None, N2min=1e-7,
                do_conv=False, kappa_alt=None, stream=None, report_nonfinite=True,
@@ -355,20 +376,40 @@ class ColumnBatch(object):
 
   def steps(self, wA, dt, nsteps=1, ops=_lib.PM_OP_TIMESTEP, vdx_in=None, b_in=None,
             lanes_per_col=0, precombined=False, arith="exact", psi_forcing=None,
-            twobasin_forcing=None):
+            twobasin_forcing=None, scheme="explicit"):
     """nsteps x (convect -> vertadvdiff -> horadv) with wA held fixed, one launch.
+    scheme: "explicit" (default: the reference's forward Euler, bit-identical to NumPy) or
+    "implicit" (`pm_column_steps_implicit`: backward Euler of the same discretisation, stable at
+    any dt; an extension with no reference counterpart, a tolerance path).  The implicit scheme
+    takes `wA` (host data, a DeviceArray or None = 0) or, with precombined=True, weff; it has no
+    horadv (vdx_in / b_in), no contracted arithmetic, no kernel-formed forcing and no
+    lanes_per_col (one wavefront per column): each is a ValueError, none is ignored.  The default
+    `ops` means convect + vertadvdiff there; any other `ops` reaches the library as given, which
+    refuses PM_OP_HORADV.
     precombined: `wA` is the output of `combine_forcing` (PM_OP_WEFF).
     psi_forcing=(Psi_iso [ncols, nz], Psi_SO [ncols/2, nz] or None) instead of `wA` (two-column
     ensembles, launches of >= 3 steps): the kernel forms wA_basin = (Psi_iso - Psi_SO) * 1e6 and
     wA_north = -Psi_iso * 1e6 itself (PM_OP_WA_PSI, example_twocol_plusSO.py:105-106).
     arith: "exact" (default: the reference's operation order, bit-identical to NumPy) or
     "contracted" (opt-in tolerance mode, PM_OP_CONTRACTED: ~1e-13 relative, ~3x faster)."""
+    check_scheme(scheme, vdx_in=vdx_in, arith=arith, psi_forcing=psi_forcing,
+                 twobasin_forcing=twobasin_forcing, b_in=b_in, lanes_per_col=lanes_per_col)
+    if scheme == "implicit" and ops == _lib.PM_OP_TIMESTEP:
+      # the default's horadv bit means "horadv iff vdx_in is given", which it is not; a caller's
+      # own PM_OP_HORADV goes through and the library refuses it
+      ops = _lib.PM_OP_CONVECT | _lib.PM_OP_VERTADVDIFF
     if precombined:
       ops = ops | _lib.PM_OP_WEFF
     if arith == "contracted":
       ops = ops | _lib.PM_OP_CONTRACTED
     elif arith != "exact":
       raise ValueError("arith must be 'exact' or 'contracted'")
+    if scheme == "implicit":
+      wA_d = self._dev(wA, "_wA")
+      d = self.descriptor()
+      check(lib.pm_column_steps_implicit(C.byref(d), wA_d.ptr if wA_d else None, float(dt),
+                                         int(nsteps), int(ops), _sh(self.stream)))
+      return
     if vdx_in is not None and b_in is None:
       raise TypeError('b_in is needed if vdx_in is provided')  # column.py:348
     if twobasin_forcing is not None:

@@ -468,6 +468,30 @@ int pm_column_steps(const pm_columns *cols, const double *wA, const double *vdx_
   }
 }
 
+int pm_column_steps_implicit(const pm_columns *cols, const double *wA, double dt, int32_t nsteps,
+                             int32_t ops, pm_stream_t stream) {
+  PM_REQUIRE(cols, "pm_column_steps_implicit: cols is NULL");
+  const pm_columns &c = *cols;
+  PM_REQUIRE(c.ncols >= 0 && c.nz >= 2 && c.nz <= 1024,
+             "pm_column_steps_implicit: bad batch shape ncols=%d nz=%d (need nz in [2,1024])",
+             c.ncols, c.nz);
+  PM_REQUIRE(c.nsel >= 1 && c.nsel <= 2, "pm_column_steps_implicit: nsel must be 1 or 2 (got %d)",
+             c.nsel);
+  PM_REQUIRE(!(ops & PM_OP_HORADV), "pm_column_steps_implicit: PM_OP_HORADV is not supported");
+  PM_REQUIRE(!(ops & PM_OP_CONTRACTED), "pm_column_steps_implicit: PM_OP_CONTRACTED is not supported");
+  PM_REQUIRE(!(ops & PM_OP_WA_PSI), "pm_column_steps_implicit: PM_OP_WA_PSI is not supported");
+  PM_REQUIRE(!(ops & PM_OP_WA_TWOBASIN),
+             "pm_column_steps_implicit: PM_OP_WA_TWOBASIN is not supported");
+  PM_REQUIRE((ops & ~(PM_OP_CONVECT | PM_OP_VERTADVDIFF | PM_OP_WEFF)) == 0,
+             "pm_column_steps_implicit: unknown op bits 0x%x", ops);
+  PM_REQUIRE(nsteps >= 0, "pm_column_steps_implicit: nsteps < 0");
+  PM_REQUIRE(isfinite(dt) && dt > 0.0, "pm_column_steps_implicit: dt must be finite and positive");
+  if (c.ncols == 0) return PM_OK;  // empty batch: nothing to do, pointers may be NULL
+  PM_REQUIRE(columns_rows_given(c), "pm_column_steps_implicit: pm_columns has a NULL required pointer");
+  if (nsteps == 0 || (ops & (PM_OP_CONVECT | PM_OP_VERTADVDIFF)) == 0) return PM_OK;
+  return column_steps_implicit(c, wA, dt, nsteps, ops, resolve_stream(stream));
+}
+
 static __global__ void k_column_weff(pm_columns c, const double *__restrict__ wA,
                               double *__restrict__ weff) {
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .columns import ColumnBatch, _HINT_DIV3_OFF, div3_licensed
+from .columns import ColumnBatch, _HINT_DIV3_OFF, check_scheme, div3_licensed
 from .device import DeviceArray, Event, Graph, Stream, _sh, launch_span
 from .equilibrium import ColumnEquiBatch
 from .psi_so import PsiSOBatch
@@ -378,8 +378,17 @@ class TwoColEnsemble(CoupledEnsemble):
 
   def __init__(self, cfg, stream=None, lanes_per_col=0, comm=None, n_total=None,
                diag_iters=None, keep_history=False, arith="exact", overlap_updates=False,
-               fused_run=None, gather="all", gather_overlap=True, forcing=None):
-    """`fused_run`: carry the members through whole stretches of the loop -- many [refresh the
+               fused_run=None, gather="all", gather_overlap=True, forcing=None,
+               scheme="explicit"):
+    """`scheme="implicit"`: the columns step with backward Euler (ColumnBatch.steps(scheme=
+    "implicit"), pm_column_steps_implicit) -- stable at any dt, an extension with no reference
+    counterpart (a tolerance path); the forcing reaches them as an array (the thermal wind's wA
+    outputs or pm_twocol_forcing, as for launches of 1-2 steps), everything else is unchanged.
+    Not with fused_run, arith="contracted" or a non-zero lanes_per_col (ValueError: the implicit
+    kernel always gives a column one wavefront).  Works with `forcing=` and under
+    run_to_steady.  (This driver captures no hipGraph -- it has no `use_graph` -- so there is
+    nothing to capture or refuse.)
+    `fused_run`: carry the members through whole stretches of the loop -- many [refresh the
     overturning, MOC_up_iters steps] intervals -- in ONE launch of the persistent per-member
     kernel (pm_twocol_run), ending a launch only where the diagnostics are gathered.  Same device
     functions as the launch sequence, bit-identical results; needs: no SO channel, exact
@@ -404,6 +413,10 @@ class TwoColEnsemble(CoupledEnsemble):
     nz = z.size
     n = self.members(cfg)
     self._check_forcing(forcing, cfg, n, fused_run=fused_run)
+    check_scheme(scheme, arith=arith, lanes_per_col=lanes_per_col)
+    if scheme == "implicit" and fused_run:
+      raise ValueError("scheme='implicit' excludes fused_run")
+    self.scheme = scheme
     rd = lambda key: self.read(cfg, key, n)  # noqa: E731
     self.n, self.nz = n, nz
     self.dt, self.M, self.nb = float(cfg['dt']), int(cfg['MOC_up_iters']), int(cfg['nb'])
@@ -472,18 +485,24 @@ class TwoColEnsemble(CoupledEnsemble):
                      wA1=self.wA_basin, wA2=self.wA_north)
 
   def _steps(self, n):
-    with launch_span(self.timer, "k_column_steps" if n >= 3 else "k_column_steps_short",
-                     self.stream):
+    name = ("k_column_implicit" if self.scheme == "implicit" else
+            "k_column_steps" if n >= 3 else "k_column_steps_short")
+    with launch_span(self.timer, name, self.stream):
       self._steps_launch(n)
 
   def _steps_launch(self, n):
-    if self.so is not None and self._overlap and n >= 3:
+    implicit = self.scheme == "implicit"
+    if self.so is not None and self._overlap and n >= 3 and not implicit:
       self.cols.steps(None, self.dt, n, lanes_per_col=self.lanes, arith=self.arith,
                       psi_forcing=(self.tw.psibz, self.so.Psi))
       return
-    if self.so is not None and self._overlap:  # a launch of 1-2 steps: the forcing as an array
+    # a launch of 1-2 steps, or the implicit scheme: the forcing as an array
+    if self.so is not None and self._overlap:
       check(lib.pm_twocol_forcing(self.n, self.nz, self.tw.psibz.ptr, self.so.Psi.ptr,
                                   self.wA.ptr, _sh(self.stream)))
+    if implicit:
+      self.cols.steps(self.wA, self.dt, n, scheme="implicit")
+      return
     self.cols.steps(self.wA, self.dt, n, lanes_per_col=self.lanes, arith=self.arith)
 
   def _run_fused(self, nsteps):

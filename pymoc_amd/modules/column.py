@@ -12,7 +12,7 @@ overturning updates (examples/example_twocol.py:85-96: 24 steps per update).  Su
 QUEUED and executed as one fused launch (one H2D, one `pm_column_steps(nsteps=k)`, one D2H)
 the moment the state is needed:
   * `col.b` is read (the attribute is a property) or assigned;
-  * the next call differs in anything -- wA values, dt, do_conv, horadv inputs, bs / bbot /
+  * the next call differs in anything -- wA values, dt, do_conv, scheme, horadv inputs, bs / bbot /
     bzbot / N2min, a re-assigned (or, for arrays, edited) kappa / Area;
   * any other pymoc_amd module object computes (`flush_all()`: they may read the array
     through an alias such as `AMOC.update(b1=basin.b)`);
@@ -88,7 +88,7 @@ class Column(object):
     self.N2min = N2min
     self._arena = None
     self._static_tok = None
-    self._q = None  # queued identical timesteps: [count, wA, dt, do_conv, params, b at opening]
+    self._q = None  # queued identical timesteps: [count, wA, dt, do_conv, params, b at opening, scheme]
     self._b = make_array(b, self.z, 'b')
     self.bz = np.gradient(self._b, z)
 
@@ -194,7 +194,8 @@ class Column(object):
     return (self.bs, self.bbot, self.bzbot, self.N2min, _static_token(self.kappa, self.z),
             _static_token(self.Area, self.z))
 
-  def _run(self, ops, do_conv, wA=None, dt=1., vdx_in=None, b_in=None, nsteps=1, params=None):
+  def _run(self, ops, do_conv, wA=None, dt=1., vdx_in=None, b_in=None, nsteps=1, params=None,
+           scheme="explicit"):
     z, nz, h = self.z, self.z.size, None
     if params is None:  # immediate call: the coefficients as they are now
       params = self._params()
@@ -213,11 +214,17 @@ class Column(object):
         _lib.PM_COL_BZBOT if bzbot is not None else 0)
     h[4 * nz + 4:].view(np.int32)[0] = flags
     self._arena.upload(h)
-    _lib.check(_lib.lib.pm_column_steps(
-        self._C.byref(self._desc), self._wA_ptr,
-        self._vdx_ptr if vdx_in is not None else None,
-        self._bin_ptr if vdx_in is not None else None, float(dt), int(nsteps), int(ops), 0,
-        None))
+    if scheme == "implicit":  # backward Euler, an extension (pm_column_steps_implicit)
+      if ops == _lib.PM_OP_TIMESTEP:  # the queue's "horadv iff vdx_in is given": it never is here
+        ops = _lib.PM_OP_CONVECT | _lib.PM_OP_VERTADVDIFF
+      _lib.check(_lib.lib.pm_column_steps_implicit(
+          self._C.byref(self._desc), self._wA_ptr, float(dt), int(nsteps), int(ops), None))
+    else:
+      _lib.check(_lib.lib.pm_column_steps(
+          self._C.byref(self._desc), self._wA_ptr,
+          self._vdx_ptr if vdx_in is not None else None,
+          self._bin_ptr if vdx_in is not None else None, float(dt), int(nsteps), int(ops), 0,
+          None))
     direct = (self._b.flags.c_contiguous and self._b.flags.writeable and
               self._b.dtype == np.float64 and self._b.size == nz)
     _lib.check(_lib.lib.pm_memcpy_d2h(self._b.ctypes.data if direct else self._out.ctypes.data,
@@ -230,7 +237,7 @@ class Column(object):
     q, self._q = self._q, None
     _pending.discard(self)
     if q is not None:
-      count, wA, dt, do_conv, params, b0 = q
+      count, wA, dt, do_conv, params, b0, scheme = q
       # A write into the array through an alias while steps were queued (`arr = col.b` once,
       # `arr[k] = ...` inside the loop): the reference would have stepped first and then taken
       # the write.  The queued steps run from the state the queue was opened with and the
@@ -241,7 +248,8 @@ class Column(object):
         vals = self._b[edited].copy()
         self._b[...] = b0
       # PM_OP_TIMESTEP without horadv inputs = convect + vertadvdiff on the fused fast path
-      self._run(_lib.PM_OP_TIMESTEP, do_conv, wA=wA, dt=dt, nsteps=count, params=params)
+      self._run(_lib.PM_OP_TIMESTEP, do_conv, wA=wA, dt=dt, nsteps=count, params=params,
+                scheme=scheme)
       if edited is not None:
         self._b[edited] = vals
 
@@ -261,7 +269,12 @@ class Column(object):
     self._flush()
     self._run(_lib.PM_OP_HORADV, False, dt=dt, vdx_in=vdx_in, b_in=b_in)
 
-  def timestep(self, wA=0., dt=1., do_conv=False, vdx_in=None, b_in=None):
+  def timestep(self, wA=0., dt=1., do_conv=False, vdx_in=None, b_in=None, scheme="explicit"):
+    """The reference's timestep (column.py:315-348).  `scheme="implicit"` (an extension, not in the
+    reference) takes the step with backward Euler instead -- stable at any dt, a tolerance path;
+    it has no horadv (ValueError with vdx_in)."""
+    from ..columns import check_scheme
+    check_scheme(scheme, vdx_in=vdx_in, b_in=b_in)
     wA = make_array(wA, self.z, 'wA')
     ops = _lib.PM_OP_CONVECT | _lib.PM_OP_VERTADVDIFF
     if vdx_in is not None and b_in is None:
@@ -276,13 +289,14 @@ class Column(object):
       self._run(ops | _lib.PM_OP_HORADV, do_conv, wA=wA, dt=dt, vdx_in=vdx_in, b_in=b_in)
       return
     if not LAZY:
-      self._run(ops, do_conv, wA=wA, dt=dt)
+      self._run(ops, do_conv, wA=wA, dt=dt, scheme=scheme)
       return
     # queue: identical consecutive steps fuse into one launch
     params = self._params()
     q = self._q
     if q is not None:
       if (q[0] < MAX_QUEUE and q[2] == dt and q[3] == do_conv and q[4] == params and
+          q[6] == scheme and
           (q[1] is wA or np.array_equal(q[1], wA)) and
           np.array_equal(self._b, q[5], equal_nan=True)):  # (no write through an alias since)
         q[0] += 1
@@ -292,5 +306,5 @@ class Column(object):
     # snapshotted (the caller may reuse its buffer; the reference reads it during the call)
     self._sync_statics(params)
     self._q = [1, np.array(wA, dtype=np.float64, copy=True), dt, bool(do_conv), params,
-               np.array(self._b, dtype=np.float64, copy=True)]
+               np.array(self._b, dtype=np.float64, copy=True), scheme]
     _pending.add(self)
