@@ -479,6 +479,21 @@ typedef struct pm_jn2018 {
 
 int pm_jn2018_steps(const pm_jn2018 *jn, double dt, int32_t nsteps, pm_stream_t stream);
 
+/* The same fused loop (examples/run_JansenNadeau_2018.py:229-261) with both columns advanced by
+ * backward Euler: an EXTENSION, no reference counterpart (the script's columns are forward Euler,
+ * which at its own nz = 200 cannot take its dt = 30 d).  Exactly nsteps x
+ *   [pm_jn2018_bc_switch;
+ *    pm_column_steps_implicit(cols, wA, dt, 1, PM_OP_CONVECT | PM_OP_VERTADVDIFF) on the 2n columns;
+ *    pm_so_ml_step with b_basin = the basin rows, Psi_b = Psi_SO]
+ * per member in ONE launch, wA / Psi_SO / Psi_res_b / Psi_res_n held fixed, and bit-identical to
+ * that launch sequence: b, ml.bs, ml.Psi_s, bbot, ksel, cols.nonfinite (each column's own flag)
+ * and ml.status (the last step's: 1 where the mixed layer did not step, else 2 where ml.bs is not
+ * finite).  A column's matrix is factored at launch and again only in a step whose BC switch
+ * changes its coefficient set.  2 <= nz <= 256, any ny pm_so_ml_step takes within the CU's LDS,
+ * Area per level.  PM_JN_CONTRACTED, PM_JN_SPLIT_LANES, nsteps < 0 and a dt that is not finite and
+ * positive are PM_EINVAL; the other hints are ignored; n == 0 or nsteps == 0 launches nothing.  */
+int pm_jn2018_steps_implicit(const pm_jn2018 *jn, double dt, int32_t nsteps, pm_stream_t stream);
+
 /* ------------------------------------------------------------------ whole coupled runs
  * The reference's coupled drivers are loops "every MOC_up_iters steps refresh the overturning
  * diagnostics, then step" (examples/example_twocol.py:85-96, run_JansenNadeau_2018.py:201-261).

@@ -333,6 +333,8 @@ SIGNATURES = {
     "pm_so_ml_step": (C.c_int, [C.POINTER(pm_so_ml), C.c_double, C.c_void_p]),
     "pm_jn2018_bc_switch": (C.c_int, [C.POINTER(pm_jn2018_bc), C.c_void_p]),
     "pm_jn2018_steps": (C.c_int, [C.POINTER(pm_jn2018), C.c_double, C.c_int32, C.c_void_p]),
+    "pm_jn2018_steps_implicit": (C.c_int, [C.POINTER(pm_jn2018), C.c_double, C.c_int32,
+                                           C.c_void_p]),
     "pm_twocol_run": (C.c_int, [C.POINTER(pm_twocol_loop), C.c_void_p]),
     "pm_jn2018_run": (C.c_int, [C.POINTER(pm_jn2018_loop), C.c_void_p]),
     "pm_so_tw_update": (C.c_int, [C.POINTER(pm_psi_so), C.POINTER(pm_thermwind), C.c_int32,

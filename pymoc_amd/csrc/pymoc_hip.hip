@@ -642,6 +642,18 @@ int pm_jn2018_steps(const pm_jn2018 *jn, double dt, int32_t nsteps, pm_stream_t 
   }
 }
 
+int pm_jn2018_steps_implicit(const pm_jn2018 *jn, double dt, int32_t nsteps, pm_stream_t stream) {
+  PM_REQUIRE(jn, "pm_jn2018_steps_implicit: jn is NULL");
+  const pm_jn2018 &a = *jn;
+  if (const int rc = check_jn2018("pm_jn2018_steps_implicit: jn", a)) return rc;
+  PM_REQUIRE(!(a.hints & PM_JN_CONTRACTED), "pm_jn2018_steps_implicit: PM_JN_CONTRACTED is not supported");
+  PM_REQUIRE(!(a.hints & PM_JN_SPLIT_LANES), "pm_jn2018_steps_implicit: PM_JN_SPLIT_LANES is not supported");
+  PM_REQUIRE(nsteps >= 0, "pm_jn2018_steps_implicit: nsteps %d < 0", nsteps);
+  PM_REQUIRE(isfinite(dt) && dt > 0.0, "pm_jn2018_steps_implicit: dt must be finite and positive");
+  if (a.n == 0 || nsteps == 0) return PM_OK;
+  return launch_jn2018_implicit(a, dt, nsteps, resolve_stream(stream));
+}
+
 int pm_so_tw_update(const pm_psi_so *so, const pm_thermwind *tw, int32_t tw_ops,
                     pm_stream_t stream) {
   PM_REQUIRE(so && tw, "pm_so_tw_update: NULL argument");

@@ -849,6 +849,46 @@ class JN2018Ensemble(CoupledEnsemble):
                           Psi_iso_n=self.tw.psibz2, Psi_s=self.ml.Psi_s)
 
 
+class JN2018ImplicitEnsemble(JN2018Ensemble):
+  """JN2018Ensemble with both columns advanced by backward Euler (pm_jn2018_steps_implicit): an
+  extension with no reference counterpart -- run_JansenNadeau_2018.py's columns are forward Euler,
+  which at its own nz = 200 cannot take its dt = 30 d (kappa dt / dz^2 > 1/2).  Stable at any dt;
+  a tolerance path against the explicit class, which stays the bit-identical one.
+
+  The loop, the MOC update, the recorder, the gather, `state()`, `drift_fields()`, MEMBER_KEYS,
+  RESTART_PHASE and FORCING_TARGETS are JN2018Ensemble's; only the step differs: BC switch -> both
+  columns by ColumnBatch.steps(scheme="implicit") -> mixed layer, fused over the steps between two
+  MOC updates into one launch.  The options of the explicit kernels (lanes_per_col, use_graph,
+  arith, shared_coef, fused_run, split_lanes) are not accepted."""
+
+  def __init__(self, cfg, stream=None, fused=None, comm=None, n_total=None, diag_iters=None,
+               keep_history=False, gather="all", gather_overlap=True, forcing=None):
+    """`fused`: None = the fused kernel where it applies (nz <= 256), else one step at a time
+    (pm_jn2018_bc_switch, pm_column_steps_implicit, pm_so_ml_step); False forces the latter;
+    True where the kernel does not apply is a ValueError.  The two are bit-identical.  The other
+    arguments as for JN2018Ensemble."""
+    if fused and cfg['z'].size > 256:
+      raise ValueError("fused=True needs nz <= 256 (nz=%d)" % cfg['z'].size)
+    JN2018Ensemble.__init__(self, cfg, stream=stream, fused=fused, comm=comm, n_total=n_total,
+                            diag_iters=diag_iters, keep_history=keep_history, gather=gather,
+                            gather_overlap=gather_overlap, forcing=forcing)
+
+  def _step(self):
+    check(lib.pm_jn2018_bc_switch(C.byref(self._bc), _sh(self.stream)))
+    self.cols.steps(self.wA, self.dt, 1, scheme="implicit")
+    self.ml.step(self.b_basin, self.so.Psi, self.dt)
+
+  def _jn_descriptor(self):
+    d = JN2018Ensemble._jn_descriptor(self)
+    d.hints = 0  # (the hints vouch for what the explicit kernels use)
+    return d
+
+  def _fused_steps(self, nsteps):
+    d = self._jn_descriptor()
+    with launch_span(self.timer, "k_jn2018_implicit", self.stream):
+      check(lib.pm_jn2018_steps_implicit(C.byref(d), self.dt, int(nsteps), _sh(self.stream)))
+
+
 class TwoBasinEnsemble(CoupledEnsemble):
   """twobasin_NadeauJansen.py: Atlantic, northern-sinking and Pacific columns; AMOC
   (Atl vs north) and zonal (Atl vs Pac) thermal-wind overturnings mapped to isopycnal space;
