@@ -250,6 +250,25 @@ int pm_column_steps(const pm_columns *cols, const double *wA, const double *vdx_
 int pm_column_steps_implicit(const pm_columns *cols, const double *wA, double dt, int32_t nsteps,
                              int32_t ops, pm_stream_t stream);
 
+/* pm_column_steps_implicit for the two-basin driver's three-column ensembles (rows [0, n) Atlantic,
+ * [n, 2n) north, [2n, 3n) Pacific, n = ncols / 3), the forcing formed by the kernel itself as it
+ * builds the matrix, from the AMOC's isopycnal overturnings `iso` [2n][nz] (Atlantic, north), the
+ * zonal overturning's `zon` [2n][nz] (Atlantic, Pacific) and the two sectors' Psi_SO `so` [2n][nz]
+ * (Atlantic, Pacific), all in Sv:
+ *   wA_Atl = (iso_A + zon_A - SO_A) * 1e6,  wA_north = -iso_N * 1e6,  wA_Pac = (-zon_P - SO_P) * 1e6
+ * (twobasin_NadeauJansen.py:103-105) -- pm_twobasin_forcing's operations in its order.  Like its
+ * sibling an extension and a TOLERANCE path against the reference; against the sibling it is
+ * bit-identical: the result equals pm_twobasin_forcing into an array followed by
+ * pm_column_steps_implicit on that array, for every nsteps >= 1.  Each array is read in its 2n rows
+ * only (a Pacific column takes nothing from `iso`).  ops: PM_OP_CONVECT | PM_OP_VERTADVDIFF
+ * (PM_OP_WA_TWOBASIN is implied and may be given).  PM_EINVAL: ncols not a multiple of 3, one of the
+ * three arrays NULL on a non-empty batch, PM_OP_WEFF, PM_OP_HORADV, PM_OP_CONTRACTED, PM_OP_WA_PSI
+ * or unknown op bits, nsteps < 0, a dt that is not finite and positive, nz outside [2, 1024].  An
+ * empty batch and nsteps == 0 launch nothing.                                                     */
+int pm_column_steps_implicit_twobasin(const pm_columns *cols, const double *iso, const double *zon,
+                                      const double *so, double dt, int32_t nsteps, int32_t ops,
+                                      pm_stream_t stream);
+
 /* weff[ncols][nz] = wA - d(A kappa)/dz of each column's coefficient set in use (column.py:241),
  * for pm_column_steps(..., ops | PM_OP_WEFF).                                                 */
 int pm_column_weff(const pm_columns *cols, const double *wA, double *weff, pm_stream_t stream);

@@ -22,7 +22,7 @@ from .modules import Column, Psi_Thermwind, Psi_SO, SO_ML, Equi_Column
 from . import configs
 from . import sharding
 from .ensembles import (EquiIterationEnsemble, ColumnThermwindEnsemble, TwoColEnsemble, JN2018Ensemble,
-                        JN2018ImplicitEnsemble, TwoBasinEnsemble)
+                        JN2018ImplicitEnsemble, TwoBasinEnsemble, TwoBasinSweep)
 from .forcing import ForcingSchedule
 from . import diagnostics
 from . import plotting

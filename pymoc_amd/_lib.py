@@ -322,6 +322,8 @@ SIGNATURES = {
                                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "pm_column_steps_implicit": (C.c_int, [C.POINTER(pm_columns), c_dp, C.c_double, C.c_int32,
                                            C.c_int32, C.c_void_p]),
+    "pm_column_steps_implicit_twobasin": (C.c_int, [C.POINTER(pm_columns), c_dp, c_dp, c_dp,
+                                                    C.c_double, C.c_int32, C.c_int32, C.c_void_p]),
     "pm_column_weff": (C.c_int, [C.POINTER(pm_columns), c_dp, c_dp, C.c_void_p]),
     "pm_column_kernel_shape": (C.c_int, [C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

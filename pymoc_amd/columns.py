@@ -440,3 +440,21 @@ class ColumnBatch(object):
                               vdx_d.ptr if vdx_d else None,
                               bin_d.ptr if bin_d else None, float(dt), int(nsteps),
                               int(ops), int(lanes_per_col), _sh(self.stream)))
+
+  def steps_implicit_twobasin(self, dt, nsteps, iso, zon, so):
+    """nsteps backward-Euler steps (convect -> vertadvdiff) of a three-column two-basin batch (rows
+    [0, n) Atlantic, [n, 2n) north, [2n, 3n) Pacific), the forcing formed by the kernel from the
+    DeviceArrays `iso`, `zon`, `so` ([2n, nz] each: the AMOC's and the zonal overturning's isopycnal
+    overturnings and the two sectors' Psi_SO) -- pm_column_steps_implicit_twobasin: bit-identical
+    to pm_twobasin_forcing into an array and steps(array, scheme="implicit"); like every implicit
+    path an extension with no reference counterpart, a tolerance path."""
+    for name, a in (("iso", iso), ("zon", zon), ("so", so)):
+      if not isinstance(a, DeviceArray):
+        raise TypeError("%s must be a DeviceArray of [2 ncols / 3, nz]" % name)
+      if a.nbytes < 2 * (self.ncols // 3) * self.nz * 8:
+        raise ValueError("%s holds fewer than 2 ncols / 3 = %d rows of %d levels"
+                         % (name, 2 * (self.ncols // 3), self.nz))
+    d = self.descriptor()
+    check(lib.pm_column_steps_implicit_twobasin(
+        C.byref(d), iso.ptr, zon.ptr, so.ptr, float(dt), int(nsteps),
+        int(_lib.PM_OP_CONVECT | _lib.PM_OP_VERTADVDIFF), _sh(self.stream)))

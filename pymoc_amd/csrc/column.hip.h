@@ -1563,7 +1563,7 @@ int column_steps_g64(const ColumnPlan &pl, const pm_columns &c, const double *wA
                      const double *vdx, const double *bin, double dt, int nsteps, int ops,
                      hipStream_t st);
 // backward Euler of vertadvdiff, an extension without a reference counterpart (column_implicit.hip)
-int column_steps_implicit(const pm_columns &c, const double *wA, double dt, int nsteps, int ops,
-                          hipStream_t st);
+int column_steps_implicit(const pm_columns &c, const double *wA, const double *zon,
+                          const double *so, double dt, int nsteps, int ops, hipStream_t st);
 
 }  // namespace pm

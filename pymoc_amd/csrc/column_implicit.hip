@@ -29,6 +29,10 @@
 //   3. back-substitution: x_j from u_j, X', X.
 // P = 1 (nz <= 64) is plain PCR.  No LDS, no barrier; registers only (the build reports the
 // scratch size of every instantiation: 0 bytes for nz <= 256).
+// pm_column_steps_implicit_twobasin launches the same instantiations with PM_OP_WA_TWOBASIN set: the
+// rows' forcing is then formed from the two-basin driver's three overturning arrays as the matrix
+// is built (imp_twobasin_wa), in pm_twobasin_forcing's operation order -- bit-identical to that
+// launch into an array followed by pm_column_steps_implicit on the array.
 // The device functions (row construction, factors, solve, the step) live in column_implicit.hip.h,
 // which the fused Jansen & Nadeau loop (jn2018_implicit.hip) includes too.
 #include "column_implicit.hip.h"
@@ -39,6 +43,8 @@ namespace pm {
 template <int P>
 __global__ __launch_bounds__(256) void k_column_implicit(pm_columns c,
                                                          const double *__restrict__ wA_g,
+                                                         const double *__restrict__ zon_g,
+                                                         const double *__restrict__ so_g,
                                                          double dt, int nsteps, int ops) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int col = __builtin_amdgcn_readfirstlane(
@@ -64,7 +70,7 @@ __global__ __launch_bounds__(256) void k_column_implicit(pm_columns c,
   ImpFactors<P> f;
   double q1 = 0.0;  // PM_COL_BZBOT: row 1's right-hand side is b_1 + q1
   if (ops & PM_OP_VERTADVDIFF)
-    imp_build<P>(f, q1, c, wA_g, col, sel, dt, ops, k.use_bzbot, k.bzbot, lane);
+    imp_build<P>(f, q1, c, wA_g, col, sel, dt, ops, k.use_bzbot, k.bzbot, lane, zon_g, so_g);
 
   for (int s = 0; s < nsteps; ++s) imp_step<P>(f, b, z, k, bbot, q1, ops, lane, nz, c.z);
 
@@ -83,14 +89,17 @@ __global__ __launch_bounds__(256) void k_column_implicit(pm_columns c,
   }
 }
 
-int column_steps_implicit(const pm_columns &c, const double *wA, double dt, int nsteps, int ops,
-                          hipStream_t st) {
+// wA alone: the forcing as an array; with zon / so (ops carries PM_OP_WA_TWOBASIN): the three
+// overturning arrays of a two-basin batch
+int column_steps_implicit(const pm_columns &c, const double *wA, const double *zon,
+                          const double *so, double dt, int nsteps, int ops, hipStream_t st) {
   constexpr int WPB = 4;  // columns (waves) per block
   const unsigned grid = (unsigned)((c.ncols + WPB - 1) / WPB);
   const int need = (c.nz + WAVE - 1) / WAVE;
 #define PM_IMP_CASE(PP)                                                                     \
   if (need <= PP)                                                                           \
-    return launch_dyn(k_column_implicit<PP>, grid, WPB * WAVE, 0, st, c, wA, dt, nsteps, ops);
+    return launch_dyn(k_column_implicit<PP>, grid, WPB * WAVE, 0, st, c, wA, zon, so, dt,    \
+                      nsteps, ops);
   PM_IMP_CASE(1)
   PM_IMP_CASE(2)
   PM_IMP_CASE(3)

@@ -126,13 +126,34 @@ __device__ __forceinline__ void imp_solve(const ImpFactors<P> &f, const double (
   }
 }
 
+// Level i's forcing of column `col` of a two-basin batch (rows [0, n) Atlantic, [n, 2n) north,
+// [2n, 3n) Pacific, n = ncols / 3) from the overturnings, pm_twobasin_forcing's operations in its
+// order (twobasin_NadeauJansen.py:103-105): iso / zon / so are [2n][nz].  Every load sits inside its
+// row group's branch (`col` is wave-uniform: the branches are scalar): a Pacific column issues no
+// load from `iso`, which has no row for it.
+__device__ __forceinline__ double imp_twobasin_wa(const double *__restrict__ iso,
+                                                  const double *__restrict__ zon,
+                                                  const double *__restrict__ so, int col, int third,
+                                                  int nz, int i) {
+  if (col < third) {
+    const size_t k = (size_t)col * nz + i;
+    return (iso[k] + zon[k] - so[k]) * 1e6;
+  }
+  if (col < 2 * third) return (-iso[(size_t)col * nz + i]) * 1e6;
+  const size_t k = (size_t)(col - third) * nz + i;
+  return (-zon[k] - so[k]) * 1e6;
+}
+
 // The rows of column `col`'s system with coefficient set `sel`, factored into f; q1 = what
-// PM_COL_BZBOT adds to row 1's right-hand side.  Static data, wA and dt only.
+// PM_COL_BZBOT adds to row 1's right-hand side.  Static data, wA and dt only.  Under
+// PM_OP_WA_TWOBASIN (pm_column_steps_implicit_twobasin only) wA_g / zon_g / so_g are the three
+// overturning arrays and the forcing is formed here.
 template <int P>
 __device__ __forceinline__ void imp_build(ImpFactors<P> &f, double &q1, const pm_columns &c,
                                           const double *__restrict__ wA_g, int col, int sel,
                                           double dt, int ops, bool use_bzbot, double bzbot,
-                                          int lane) {
+                                          int lane, const double *__restrict__ zon_g = nullptr,
+                                          const double *__restrict__ so_g = nullptr) {
   const int nz = c.nz;
   const size_t base = (size_t)col * nz;
   const size_t coef = (size_t)sel * c.ncols * nz + base;
@@ -146,7 +167,9 @@ __device__ __forceinline__ void imp_build(ImpFactors<P> &f, double &q1, const pm
       const double z0 = c.z[i], dzm = z0 - c.z[i - 1], dzp = c.z[i + 1] - z0;
       const double dzc = 0.5 * (dzp + dzm);
       const double kap = c.kappa[coef + i];
-      const double wa = wA_g ? wA_g[base + i] : 0.0;
+      const double wa = (ops & PM_OP_WA_TWOBASIN)
+                            ? imp_twobasin_wa(wA_g, zon_g, so_g, col, c.ncols / 3, nz, i)
+                            : (wA_g ? wA_g[base + i] : 0.0);
       const double weff = (ops & PM_OP_WEFF) ? wa : wa - c.dAkappa[coef + i];
       const double w = weff / c.area[base + i];
       const double cl = (w < 0.0 ? 0.0 : w / dzm) + kap / (dzc * dzm);

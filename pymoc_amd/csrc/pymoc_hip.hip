@@ -489,7 +489,43 @@ int pm_column_steps_implicit(const pm_columns *cols, const double *wA, double dt
   if (c.ncols == 0) return PM_OK;  // empty batch: nothing to do, pointers may be NULL
   PM_REQUIRE(columns_rows_given(c), "pm_column_steps_implicit: pm_columns has a NULL required pointer");
   if (nsteps == 0 || (ops & (PM_OP_CONVECT | PM_OP_VERTADVDIFF)) == 0) return PM_OK;
-  return column_steps_implicit(c, wA, dt, nsteps, ops, resolve_stream(stream));
+  return column_steps_implicit(c, wA, nullptr, nullptr, dt, nsteps, ops, resolve_stream(stream));
+}
+
+int pm_column_steps_implicit_twobasin(const pm_columns *cols, const double *iso, const double *zon,
+                                      const double *so, double dt, int32_t nsteps, int32_t ops,
+                                      pm_stream_t stream) {
+  PM_REQUIRE(cols, "pm_column_steps_implicit_twobasin: cols is NULL");
+  const pm_columns &c = *cols;
+  PM_REQUIRE(c.ncols >= 0 && c.nz >= 2 && c.nz <= 1024,
+             "pm_column_steps_implicit_twobasin: bad batch shape ncols=%d nz=%d (need nz in [2,1024])",
+             c.ncols, c.nz);
+  PM_REQUIRE(c.ncols % 3 == 0,
+             "pm_column_steps_implicit_twobasin: ncols=%d is not a multiple of 3 (Atlantic, northern "
+             "and Pacific rows)", c.ncols);
+  PM_REQUIRE(c.nsel >= 1 && c.nsel <= 2,
+             "pm_column_steps_implicit_twobasin: nsel must be 1 or 2 (got %d)", c.nsel);
+  PM_REQUIRE(!(ops & PM_OP_WEFF),
+             "pm_column_steps_implicit_twobasin: PM_OP_WEFF is not supported (the forcing is formed "
+             "from the overturnings)");
+  PM_REQUIRE(!(ops & PM_OP_HORADV), "pm_column_steps_implicit_twobasin: PM_OP_HORADV is not supported");
+  PM_REQUIRE(!(ops & PM_OP_CONTRACTED),
+             "pm_column_steps_implicit_twobasin: PM_OP_CONTRACTED is not supported");
+  PM_REQUIRE(!(ops & PM_OP_WA_PSI), "pm_column_steps_implicit_twobasin: PM_OP_WA_PSI is not supported");
+  // (PM_OP_WA_TWOBASIN is what this entry means: given or not, it is set below)
+  PM_REQUIRE((ops & ~(PM_OP_CONVECT | PM_OP_VERTADVDIFF | PM_OP_WA_TWOBASIN)) == 0,
+             "pm_column_steps_implicit_twobasin: unknown op bits 0x%x", ops);
+  PM_REQUIRE(nsteps >= 0, "pm_column_steps_implicit_twobasin: nsteps < 0");
+  PM_REQUIRE(isfinite(dt) && dt > 0.0,
+             "pm_column_steps_implicit_twobasin: dt must be finite and positive");
+  if (c.ncols == 0) return PM_OK;  // empty batch: nothing to do, pointers may be NULL
+  PM_REQUIRE(iso && zon && so,
+             "pm_column_steps_implicit_twobasin: an overturning array (iso, zon, so) is NULL");
+  PM_REQUIRE(columns_rows_given(c),
+             "pm_column_steps_implicit_twobasin: pm_columns has a NULL required pointer");
+  if (nsteps == 0 || (ops & (PM_OP_CONVECT | PM_OP_VERTADVDIFF)) == 0) return PM_OK;
+  return column_steps_implicit(c, iso, zon, so, dt, nsteps, ops | PM_OP_WA_TWOBASIN,
+                               resolve_stream(stream));
 }
 
 static __global__ void k_column_weff(pm_columns c, const double *__restrict__ wA,

@@ -5,6 +5,8 @@ The reference has no driver class: the loops live in examples/*
 classes here reproduce those loops' order of operations and cadence exactly:
   JN2018Ensemble           examples/run_JansenNadeau_2018.py:201-261 (config 5)
   TwoBasinEnsemble         examples/twobasin_NadeauJansen.py:99-122
+  TwoBasinSweep            the same loop with per-member cfg reading, steady runs, forcing
+                           schedules and an implicit column step
   ColumnThermwindEnsemble  examples/example_timestepping.py:73-80   (BASELINE config 1)
   EquiIterationEnsemble    examples/example_iteration.py:59-68      
   TwoColEnsemble           examples/example_twocol.py:85-96         (config 3)
@@ -161,9 +163,11 @@ class CoupledEnsemble(object):
   None: the driver's constructor reads its cfg by itself and cannot be restarted on a subset.
 
   FORCING_TARGETS is the single statement of what a `forcing=ForcingSchedule(...)` may set:
-    name -> (the device array, as an attribute path from the driver; the group of n rows its
-             first row starts; the row length: None = one value per member, "y" = a profile on
-             cfg['y'], "tau" = whichever of the two the batch's tau is)
+    name -> a tuple of destinations, each (the device array, as an attribute path from the
+            driver; the group of n rows its first row starts; the row length: None = one value per
+            member, "y" = a profile on cfg['y'], "tau" = whichever of the two the batch's tau is).
+            A value the driver keeps in more than one place has one destination for each (all of
+            one row length); the schedule's values are uploaded once per name.
   None: the driver takes no schedule."""
 
   NGROUPS = 2
@@ -219,7 +223,8 @@ class CoupledEnsemble(object):
   def forcing_lengths(cls, cfg, n):
     """name -> row length of the targets a schedule may name for this cfg (host only)."""
     out = {}
-    for name, (_, _, axis) in cls.FORCING_TARGETS.items():
+    for name, dests in cls.FORCING_TARGETS.items():
+      axis = dests[0][2]  # (one row length per name)
       if axis is None:
         out[name] = 1
       elif cls._has_channel(cfg):
@@ -246,11 +251,12 @@ class CoupledEnsemble(object):
     n, lengths = self.n, self.forcing_lengths(cfg, self.n)
     targets = {}
     for name in forcing.values:
-      path, group, _ = self.FORCING_TARGETS[name]
-      a = self
-      for attr in path.split("."):
-        a = getattr(a, attr)
-      targets[name] = (a, group * n, lengths[name])
+      targets[name] = []
+      for path, group, _ in self.FORCING_TARGETS[name]:
+        a = self
+        for attr in path.split("."):
+          a = getattr(a, attr)
+        targets[name].append((a, group * n, lengths[name]))
     self._forcing = forcing.bind(n, targets, stream=self.stream)
     # PM_COL_STATIC_IN_RANGE was derived from the cfg's bs; it stays only where every value the
     # schedule can write is zero or inside the exact-division window [2^-200, 2^200]: knots that
@@ -369,8 +375,8 @@ class TwoColEnsemble(CoupledEnsemble):
   # after the update that follows step s - 1 (example_twocol.py:85-96): the constructor's own
   # update is the one at a restart
   RESTART_PHASE = 1
-  FORCING_TARGETS = dict(bs=("cols.bs", 0, None), bs_north=("cols.bs", 1, None),
-                         tau=("so.tau", 0, "tau"), bs_SO=("bs_SO", 0, "y"))
+  FORCING_TARGETS = dict(bs=(("cols.bs", 0, None),), bs_north=(("cols.bs", 1, None),),
+                         tau=(("so.tau", 0, "tau"),), bs_SO=(("bs_SO", 0, "y"),))
 
   @classmethod
   def _has_channel(cls, cfg):
@@ -591,9 +597,9 @@ class JN2018Ensemble(CoupledEnsemble):
                      bs_SO0=("rows", "y"))
   # after step s's MOC update, before the step (run_JansenNadeau_2018.py:204-217)
   RESTART_PHASE = 0
-  FORCING_TARGETS = dict(bs=("cols.bs", 0, None), bs_north=("cols.bs", 1, None),
-                         tau=("so.tau", 0, "tau"), b_rest=("ml.b_rest", 0, "y"),
-                         surflux=("ml.surflux", 0, "y"))
+  FORCING_TARGETS = dict(bs=(("cols.bs", 0, None),), bs_north=(("cols.bs", 1, None),),
+                         tau=(("so.tau", 0, "tau"),), b_rest=(("ml.b_rest", 0, "y"),),
+                         surflux=(("ml.surflux", 0, "y"),))
 
   def __init__(self, cfg, stream=None, lanes_per_col=0, use_graph=False, fused=None,
                comm=None, n_total=None, diag_iters=None, keep_history=False, arith="exact",
@@ -1063,3 +1069,113 @@ class TwoBasinEnsemble(CoupledEnsemble):
 
   def state(self):
     return self._download(**self.fields())
+
+
+class TwoBasinSweep(TwoBasinEnsemble):
+  """TwoBasinEnsemble with what the other coupled drivers have: the cfg read per member by a
+  stated rule (MEMBER_KEYS, so `restrict` / `subset` / `run_to_steady` work), a restart point, a
+  `forcing=ForcingSchedule(...)` and `scheme="implicit"`.  With neither `forcing` nor `scheme` it
+  IS the parent: the same launches in the same order, bit-identical `fields()` / `state()`.
+
+  Restart point (RESTART_PHASE = 1): the loop is `step; if ii % M == 0: update`
+  (twobasin_NadeauJansen.py:99-122), the two-column shape, so a member can be restarted at
+  s = 1 (mod MOC_up_iters), after the update that follows step s - 1.  The parent's constructor
+  forms its first AMOC against cfg['b2_init'] (the script's :64), not against the northern column;
+  `subset` therefore hands the new ensemble its members' CURRENT northern rows as `b2_init`, so the
+  constructor's own update is the update after step s - 1 on the carried-over columns, and the
+  subset comes back with the overturnings of its own three columns.  (`bbot` and `N2min` stay
+  shared scalars, as in the parent.)
+
+  `forcing`: bs (the Atlantic and Pacific columns share it, :41-47: two destinations), bs_north,
+  tau (both sectors' Psi_SO: two destinations) and bs_SO (the one array both sectors read), applied
+  by the rule of `_apply_forcing`: at s = 0 and s = 1 (mod MOC_up_iters), ahead of the steps;
+  the constructor's own update uses the cfg's values.  While a schedule is bound the loop runs
+  launch by launch: no hipGraph is captured (`use_graph` with `overlap_updates` is the slower
+  option anyway, see the parent's constructor).
+
+  `scheme="implicit"`: the three column groups step with backward Euler (pm_twobasin_forcing and
+  pm_column_steps_implicit on the array -- the default, measured no slower -- or
+  pm_column_steps_implicit_twobasin, the forcing formed in the kernel, bit-identical:
+  IMPLICIT_FORMED chooses).  Updates,
+  gather, forcing and steady runs are unchanged.  Like the other implicit paths this is an
+  EXTENSION with no reference counterpart -- the script's columns are forward Euler, which above
+  about nz = 125 cannot take its own dt = 30 d -- and a tolerance path; the default stays explicit
+  and bit-identical.  Not with arith="contracted" or a non-zero lanes_per_col (ValueError)."""
+
+  MEMBER_KEYS = dict(kappa=("rows", "z"), A_Atl=("rows", "z"), A_north=("rows", "z"),
+                     A_Pac=("rows", "z"), b_Atl0=("rows", "z"), b_north0=("rows", "z"),
+                     b_Pac0=("rows", "z"), b2_init=("rows", "z"), bs=("vec",), bs_north=("vec",),
+                     tau=("vec",), K=("vec",), bs_SO=("rows", "y"))
+  RESTART_PHASE = 1
+  FORCING_TARGETS = dict(bs=(("cols.bs", 0, None), ("cols.bs", 2, None)),
+                         bs_north=(("cols.bs", 1, None),),
+                         tau=(("so_atl.tau", 0, "tau"), ("so_pac.tau", 0, "tau")),
+                         bs_SO=(("bs_SO", 0, "y"),))
+  # the implicit step forms its forcing in the kernel (True) or reads it from pm_twobasin_forcing's
+  # array (False): bit-identical.  Measured per interval at 2048 x nz = 200: formed 171.6 us, array
+  # 167.8 us (DESIGN.md section 15) -- formed is not faster, so the driver takes the array path
+  IMPLICIT_FORMED = False
+
+  def __init__(self, cfg, stream=None, lanes_per_col=0, comm=None, n_total=None,
+               diag_iters=None, keep_history=False, arith="exact", overlap_updates=False,
+               gather="all", gather_overlap=True, use_graph=True, forcing=None,
+               scheme="explicit"):
+    n = self.members(cfg)
+    self._check_forcing(forcing, cfg, n)
+    check_scheme(scheme, arith=arith, lanes_per_col=lanes_per_col)
+    self.scheme = scheme
+    # every per-member key as an explicit [n, ...] array by its rule: the parent's own reading of
+    # such arrays is the identity
+    cfg = dict(cfg, **{key: self.read(cfg, key, n) for key in self.MEMBER_KEYS})
+    TwoBasinEnsemble.__init__(self, cfg, stream=stream, lanes_per_col=lanes_per_col, comm=comm,
+                              n_total=n_total, diag_iters=diag_iters, keep_history=keep_history,
+                              arith=arith, overlap_updates=overlap_updates, gather=gather,
+                              gather_overlap=gather_overlap, use_graph=use_graph)
+    self._bind_forcing(forcing, cfg)  # (behind the constructor's update: it used the cfg's values)
+
+  def drift_fields(self):
+    nz = self.nz
+    return [("b_Atl", self.b_Atl, nz, nz), ("b_north", self.b_north, nz, nz),
+            ("b_Pac", self.b_Pac, nz, nz)]
+
+  def capture_fields(self):
+    nz = self.nz
+    return self.drift_fields() + [
+        ("Psi_AMOC", self.amoc.Psi, nz, nz), ("Psi_ZOC", self.zoc.Psi, nz, nz),
+        ("Psi_SO_Atl", self.so_atl.Psi, nz, nz), ("Psi_SO_Pac", self.so_pac.Psi, nz, nz)]
+
+  def subset(self, keep, cfg, kw):
+    # the constructor's first AMOC is formed against b2_init: at a restart point that is the
+    # current northern column (the class docstring's restart rule)
+    cfg = dict(cfg, b2_init=self.b_north.download(stream=self.stream))
+    return CoupledEnsemble.subset(self, keep, cfg, kw)
+
+  def _steps(self, n):
+    if self.scheme != "implicit":
+      return TwoBasinEnsemble._steps(self, n)
+    if self.IMPLICIT_FORMED:
+      self.cols.steps_implicit_twobasin(self.dt, n, self.amoc.psibz, self.zoc.psibz, self._so_psi)
+      return
+    if not self._wA_fresh:
+      self._form_forcing()
+    self.cols.steps(self.wA, self.dt, n, scheme="implicit")
+
+  def _span(self, n):
+    if self.scheme == "implicit":
+      return "k_column_implicit_twobasin" if self.IMPLICIT_FORMED else "k_column_implicit"
+    return "k_column_steps" if n >= 3 else "k_column_steps_short"
+
+  def run(self, nsteps):
+    if self._forcing is None and self.scheme == "explicit":
+      return TwoBasinEnsemble.run(self, nsteps)
+    remaining = int(nsteps)
+    while remaining > 0:
+      self._apply_forcing()
+      n = self._interval(remaining)
+      with launch_span(self.timer, self._span(n), self.stream):
+        self._steps(n)
+      self.ii += n
+      remaining -= n
+      if (self.ii - 1) % self.M == 0:
+        self._update()
+        self._gather_if_due(self.ii - 1)

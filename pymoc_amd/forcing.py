@@ -73,8 +73,13 @@ class ForcingSchedule(object):
 
   def bind(self, n, targets, stream=None):
     """Upload the values and return the BoundForcing that writes them: `targets` maps each name
-    of this schedule to (DeviceArray, first row, row length)."""
-    per = self.check({k: ln for k, (_, _, ln) in targets.items()}, n)
+    of this schedule to (DeviceArray, first row, row length), or to a list of such destinations
+    of one row length (a value the driver keeps in more than one place)."""
+    targets = {k: [d] if isinstance(d, tuple) else list(d) for k, d in targets.items()}
+    for k, dests in targets.items():
+      if len({ln for _, _, ln in dests}) != 1:
+        raise ValueError("forcing target %r: its destinations differ in row length" % k)
+    per = self.check({k: dests[0][2] for k, dests in targets.items()}, n)
     return BoundForcing(self, n, targets, per, stream)
 
 
@@ -85,18 +90,25 @@ class BoundForcing(object):
     self.schedule, self.n = schedule, int(n)
     self.knots = schedule.t  # host array the descriptor points to: kept alive here
     d = self.desc = _lib.pm_forcing()
-    d.n, d.K, d.ntargets, d.reserved = self.n, schedule.K, len(per_member), 0
+    ndest = sum(len(targets[key]) for key in per_member)
+    if ndest > _lib.PM_FORCING_MAX_TARGETS:
+      raise ValueError("a schedule writes at most %d destinations (%d here)"
+                       % (_lib.PM_FORCING_MAX_TARGETS, ndest))
+    d.n, d.K, d.ntargets, d.reserved = self.n, schedule.K, ndest, 0
     d.knots = self.knots.ctypes.data
     self.arrays = []
-    for i, (key, per) in enumerate(per_member.items()):
-      dst, row0, ln = targets[key]
-      if (row0 + self.n) * ln * 8 > dst.nbytes or dst.dtype != np.float64:
-        raise ValueError("forcing target %r: rows [%d, %d) of %d values lie outside its array"
-                         % (key, row0, row0 + self.n, ln))
-      vals = DeviceArray.from_host(schedule.values[key], stream=stream)
-      self.arrays.append((dst, vals))  # (the targets must outlive the descriptor)
-      g = d.target[i]
-      g.dst, g.row0, g.values, g.len, g.per_member = dst.ptr, int(row0), vals.ptr, int(ln), int(per)
+    i = 0
+    for key, per in per_member.items():
+      vals = DeviceArray.from_host(schedule.values[key], stream=stream)  # one upload per name
+      for dst, row0, ln in targets[key]:
+        if (row0 + self.n) * ln * 8 > dst.nbytes or dst.dtype != np.float64:
+          raise ValueError("forcing target %r: rows [%d, %d) of %d values lie outside its array"
+                           % (key, row0, row0 + self.n, ln))
+        self.arrays.append((dst, vals))  # (the targets must outlive the descriptor)
+        g = d.target[i]
+        g.dst, g.row0, g.values, g.len, g.per_member = (dst.ptr, int(row0), vals.ptr, int(ln),
+                                                        int(per))
+        i += 1
 
   def apply(self, t, stream=None):
     check(lib.pm_forcing_apply(C.byref(self.desc), float(t), _sh(stream)))

@@ -2,7 +2,7 @@
 
 The reference's equilibrium experiments step for a fixed, long time (run_JansenNadeau_2018.py:96-97
 12 000 years, example_twocol.py:32 4 000 years) because they have no test for "done".
-`run_to_steady` steps a JN2018Ensemble or TwoColEnsemble and, every `check_every` steps, measures
+`run_to_steady` steps a JN2018Ensemble, TwoColEnsemble or TwoBasinSweep and, every `check_every` steps, measures
 each member's drift -- the largest change of its prognostic profiles since the last check, in
 buoyancy units per 360-day year -- with one launch of pm_steady_check.  A member whose drift stays
 at or below its tolerance for `consecutive` checks is retired: its state and overturning at that
@@ -13,7 +13,8 @@ Checks fall only on states the loop can be restarted from exactly (DESIGN.md sec
   JN2018Ensemble  at s = 0 (mod MOC_up_iters), after that step's MOC update, before the step
                   (run_JansenNadeau_2018.py:204-217);
   TwoColEnsemble  at s = 1 (mod MOC_up_iters), after the update that follows step s - 1
-                  (example_twocol.py:85-96).
+                  (example_twocol.py:85-96);
+  TwoBasinSweep   likewise at s = 1 (mod MOC_up_iters) (twobasin_NadeauJansen.py:99-122).
 Members never interact and every path through the kernels is bit-identical, so a member's
 captured state equals a plain run's after the same number of steps, compacted or not.
 """
@@ -37,8 +38,8 @@ def _restartable(cls):
   """`cls` if it states how its cfg is read per member and where it can be restarted
   (CoupledEnsemble.MEMBER_KEYS, RESTART_PHASE)."""
   if not (isinstance(cls, type) and issubclass(cls, CoupledEnsemble) and cls.MEMBER_KEYS):
-    raise ValueError("run_to_steady supports JN2018Ensemble and TwoColEnsemble, not %r"
-                     % getattr(cls, "__name__", cls))
+    raise ValueError("run_to_steady supports JN2018Ensemble and TwoColEnsemble (and their "
+                     "subclasses) and TwoBasinSweep, not %r" % getattr(cls, "__name__", cls))
   return cls
 
 
@@ -88,7 +89,8 @@ class SteadyResult(object):
     status        int32[n]  RUNNING never appears: CONVERGED, NONFINITE or MAXSTEPS
     steps         int64[n]  steps taken when the member retired
     drift         float64[n] its drift at that check (buoyancy per 360-day year; NaN if NONFINITE)
-    fields        name -> [n, len]: the captured rows (drift fields, Psi, Psi_SO)
+    fields        name -> [n, len]: the captured rows (drift fields, Psi, Psi_SO; for
+                  TwoBasinSweep the three columns and the four overturnings)
     compactions   [(step, rows_before, rows_after)]
     member_steps  rows x steps actually stepped"""
 
@@ -192,8 +194,8 @@ class _Run(object):
 
 def run_to_steady(cls, cfg, tol, max_steps, check_every=None, consecutive=1, compact_below=0.5,
                   **ensemble_kwargs):
-  """Step `cls(cfg, **ensemble_kwargs)` (JN2018Ensemble or TwoColEnsemble, with or without the
-  SO channel) until every member has converged, gone non-finite or reached `max_steps`.
+  """Step `cls(cfg, **ensemble_kwargs)` (JN2018Ensemble, TwoColEnsemble with or without the
+  SO channel, or TwoBasinSweep) until every member has converged, gone non-finite or reached `max_steps`.
 
   tol           drift tolerance, buoyancy units per 360-day year: a scalar or one per member
   max_steps     cap; the last check is on the last restartable step <= max_steps
