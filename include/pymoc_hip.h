@@ -1071,6 +1071,57 @@ struct pm_forcing {
 /* the struct is named by its tag only, as pm_steady_check's is */
 int pm_forcing_apply(const struct pm_forcing *f, double t, pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-member indices of rows (pymoc_amd.RowIndices / IndexRecorder), ONE launch: up to
+ * PM_INDICES_MAX specifications evaluated for every member, written as
+ *   value[s][m] (fp64) and pos[s][m] (int32),  s < nspec, m < n
+ * at the caller's addresses -- a recorder passes record k of its device series, so a sample is
+ * this launch alone.  (no counterpart: what a user computes from the profiles after the loop,
+ * `np.max(AMOC.Psi)`, `z[np.argmax(AMOC.Psi)]`, `np.interp(-1000., z, basin.b)`.)
+ *   spec      HOST copy of the table: every call checks it;
+ *   spec_dev  the same nspec entries in DEVICE memory, uploaded once by the table's owner: the
+ *             kernel walks the table in memory (as a kernel argument indexed at run time it would
+ *             be copied to scratch).
+ * An entry names rows `stride` doubles apart (row m of the source at src + m * stride: the drivers'
+ * fields are row views into stacked arrays), their length nlev, the axis of the levels (device,
+ * nlev doubles), the inclusive window lo..hi of levels and one parameter.  With r = row[lo..hi]:
+ *   PM_IDX_MAX    value = row[pos], the very bits; pos = lo + np.argmax(r): first occurrence, a
+ *                 NaN wins, the first NaN
+ *   PM_IDX_MIN    value = row[pos]; pos = lo + np.argmin(r)
+ *   PM_IDX_AT     value = np.interp(param, axis, row) over the WHOLE row (lo, hi unused), bit for
+ *                 bit, for a strictly increasing axis; pos = -1
+ *   PM_IDX_CROSS  the level c = param: if row[hi] == c: value = axis[hi], pos = hi.  Otherwise
+ *                 pos = the largest i in [lo, hi - 1] with (row[i] - c <= 0 < row[i+1] - c) or
+ *                 (row[i] - c >= 0 > row[i+1] - c), t = (c - row[i]) / (row[i+1] - row[i]) and
+ *                 value = axis[i] + t * (axis[i+1] - axis[i]), uncontracted.  No such i: NaN, -1
+ *   PM_IDX_MEAN   value = S / (axis[hi] - axis[lo]), S = sum over i in [lo, hi - 1] of
+ *                 0.5 * (row[i] + row[i+1]) * (axis[i+1] - axis[i]); hi == lo: row[lo]; pos = -1.
+ *                 The summation order is the kernel's own: the one index that is a tolerance path.
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): n >= 1, 1 <= nspec <=
+ * PM_INDICES_MAX, nlev >= 1, 0 <= lo <= hi < nlev, stride >= nlev, no NULL pointer, kind known.
+ * That rows [0, n) of every source lie inside its allocation is the caller's to ensure.         */
+#define PM_INDICES_MAX 32
+#define PM_IDX_MAX 0
+#define PM_IDX_MIN 1
+#define PM_IDX_AT 2
+#define PM_IDX_CROSS 3
+#define PM_IDX_MEAN 4
+typedef struct pm_index_spec {
+  const double *src;                     /* device: row m at src + m * stride                     */
+  const double *axis;                    /* device [nlev]                                         */
+  int64_t stride;                        /* doubles between rows, >= nlev                         */
+  int32_t nlev, kind, lo, hi;
+  double param;                          /* PM_IDX_AT: x0; PM_IDX_CROSS: the level                */
+} pm_index_spec;
+struct pm_row_indices {
+  int32_t n, nspec;
+  const pm_index_spec *spec;             /* HOST [nspec]                                          */
+  const pm_index_spec *spec_dev;         /* DEVICE [nspec], the same entries                      */
+};
+/* the struct is named by its tag only, as pm_steady_check's is */
+int pm_row_indices(const struct pm_row_indices *d, double *value, int32_t *pos,
+                   pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -275,6 +275,21 @@ class pm_forcing(C.Structure):
               ("target", pm_forcing_target * PM_FORCING_MAX_TARGETS)]
 
 
+PM_INDICES_MAX = 32
+PM_IDX_MAX, PM_IDX_MIN, PM_IDX_AT, PM_IDX_CROSS, PM_IDX_MEAN = 0, 1, 2, 3, 4
+
+
+class pm_index_spec(C.Structure):
+  """Mirror of `struct pm_index_spec` (include/pymoc_hip.h)."""
+  _fields_ = [("src", c_dp), ("axis", c_dp), ("stride", C.c_int64), ("nlev", C.c_int32),
+              ("kind", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("param", C.c_double)]
+
+
+class pm_row_indices(C.Structure):
+  """Mirror of `struct pm_row_indices` (include/pymoc_hip.h); `spec` is a HOST address."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("spec", C.c_void_p), ("spec_dev", c_dp)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -379,6 +394,7 @@ SIGNATURES = {
                                                    C.c_void_p]),
     "pm_steady_check": (C.c_int, [C.POINTER(pm_steady_check), C.c_void_p]),
     "pm_forcing_apply": (C.c_int, [C.POINTER(pm_forcing), C.c_double, C.c_void_p]),
+    "pm_row_indices": (C.c_int, [C.POINTER(pm_row_indices), c_dp, c_dp, C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -175,6 +175,9 @@ class CoupledEnsemble(object):
   MEMBER_KEYS = None
   FORCING_TARGETS = None
   RESTART_PHASE = None  # the steps s = RESTART_PHASE (mod MOC_up_iters) can be restarted from
+  # optional indices.IndexRecorder (it attaches itself): sampled at the `_gather_if_due` sites,
+  # right after the overturning update at that step; None: no launch is added anywhere
+  indices = None
 
   @classmethod
   def members(cls, cfg):
@@ -309,8 +312,15 @@ class CoupledEnsemble(object):
     self.diag.gather(self.fields(), step=self.ii if step is None else step)
 
   def _gather_if_due(self, step):
+    if self.indices is not None:
+      self.indices.maybe_sample(step)
     if self.diag is not None and self.diag.due(step, self.diag_iters):
       self.gather_diagnostics(step)
+
+  def _no_indices_in_fused_run(self):
+    if self.indices is not None:
+      raise ValueError("an IndexRecorder does not go with fused_run=True: a persistent launch "
+                       "spans the steps the samples are taken at")
 
   def nonfinite_members(self):
     nf = self.cols.get_nonfinite().reshape(self.NGROUPS, self.n)
@@ -514,6 +524,7 @@ class TwoColEnsemble(CoupledEnsemble):
   def _run_fused(self, nsteps):
     """The same loop through pm_twocol_run: one launch per stretch that ends at a diagnostic
     gather (or at the end of the run)."""
+    self._no_indices_in_fused_run()
     M, remaining = self.M, int(nsteps)
     while remaining > 0:
       ii = self.ii
@@ -765,6 +776,7 @@ class JN2018Ensemble(CoupledEnsemble):
   def _run_fused(self, nsteps):
     """The loop through pm_jn2018_run: one launch per stretch that ends where the script samples
     its diagnostics (right after a MOC update) or at the end of the run."""
+    self._no_indices_in_fused_run()
     M, remaining = self.M, int(nsteps)
     while remaining > 0:
       ii = self.ii
@@ -815,7 +827,7 @@ class JN2018Ensemble(CoupledEnsemble):
       remaining -= n
     while remaining > 0:
       if (self._use_graph and self.recorder is None and self.diag is None and
-          self.ii % self.M == 0 and remaining >= self.M):
+          self.indices is None and self.ii % self.M == 0 and remaining >= self.M):
         if self._graph is None:
           with Graph.capture(self.stream) as cap:
             self._block()
