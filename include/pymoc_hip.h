@@ -1122,6 +1122,62 @@ struct pm_row_indices {
 int pm_row_indices(const struct pm_row_indices *d, double *value, int32_t *pos,
                    pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Stochastic forcing of an ensemble (pymoc_amd.NoiseForcing), ONE launch per application: every
+ * member's red-noise state advances by one Gaussian deviate generated on the device, and
+ * base + state * pattern is written into up to 8 destination arrays -- the arrays
+ * pm_forcing_apply writes.  (no counterpart: an extension.)
+ *
+ * Deviate xi(seed, id, j, stream): Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl
+ * constants 0x9E3779B9 / 0xBB67AE85) with
+ *   key     = { seed & 0xffffffff, seed >> 32 }
+ *   counter = { id & 0xffffffff, id >> 32, j, stream },  id = member0 + m
+ * (j: the application index the caller counts; stream: the target's position in
+ * bs, bs_north, tau, b_rest, surflux, bs_SO).  From the four output words r0..r3, in fp64:
+ *   d1 = ((r0 >> 5) * 67108864.0 + (r1 >> 6)) * 2^-53,  d2 likewise from r2, r3   (exact)
+ *   R  = sqrt(-2.0 * log(1.0 - d1))
+ *   xi = R * cos(6.283185307179586 * d2)
+ * uncontracted, in this order: d1, d2, 1.0 - d1 (in [2^-53, 1]) and the cosine's argument are
+ * exact-arithmetic results; only log and cos are the device library's (a tolerance against a host
+ * restatement: |xi - xi_host| <= 16 * 2^-53 * R).  A deviate depends on nothing but its four
+ * coordinates: not on n, on the shard, or on which other targets a launch perturbs.
+ * State, per target and member:  x_out[m] = a * x_in[m] + (sigma[m] * b) * xi, uncontracted; a
+ * and b are the caller's (a = exp(-dt / tau_corr), b = sqrt(1 - a * a); a = 0, b = 1 for white
+ * noise and for the first application on a zeroed state).  Every thread of member m recomputes
+ * x_out[m] from x_in[m]; the thread of element 0 stores it -- into the OTHER buffer, which the
+ * caller swaps with x_in between applications, so no launch reads what it writes.
+ * Value:  dst[row0 + m][i] = base[m][i] + x_out[m] * pattern[i], uncontracted (pattern [len], or
+ * [n][len] with pattern_per_member = 1; NULL: base + x_out).
+ * Entries that name the same quantity kept in two places share one state: the same `stream` and
+ * x_in give them the same x_out value; x_out and xi_out may be NULL on all but one of them.
+ * Nothing outside rows [row0, row0 + n) of a destination and [0, n) of x_out / xi_out is touched.
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): n >= 1, 1 <= ntargets <= 8,
+ * member0 >= 0; per entry len >= 1, row0 >= 0, n * len < 2^31, dst / base / sigma / x_in not NULL,
+ * no entry's x_out equal to any entry's x_in, a and b finite and in [0, 1], pattern_per_member 0
+ * or 1, 0 <= stream < PM_NOISE_STREAMS.                                                         */
+#define PM_NOISE_MAX_TARGETS 8
+#define PM_NOISE_STREAMS 6
+typedef struct pm_noise_target {
+  double *dst; int64_t row0;             /* rows [row0, row0 + n) of [.][len] are written         */
+  const double *base;                    /* device [n][len]                                       */
+  const double *pattern;                 /* device [len] or [n][len]; NULL: 1                     */
+  const double *sigma;                   /* device [n]                                            */
+  const double *x_in;                    /* device [n]                                            */
+  double *x_out;                         /* device [n], not x_in; may be NULL                     */
+  double *xi_out;                        /* device [n]: the deviates used; may be NULL            */
+  double a, b;
+  int32_t len, pattern_per_member, stream, reserved;
+} pm_noise_target;
+struct pm_noise {
+  int32_t n, ntargets;
+  uint32_t j, reserved;
+  uint64_t seed;
+  int64_t member0;
+  pm_noise_target target[PM_NOISE_MAX_TARGETS];
+};
+/* the struct is named by its tag only, as pm_steady_check's is */
+int pm_forcing_noise(const struct pm_noise *d, pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ from . import sharding
 from .ensembles import (EquiIterationEnsemble, ColumnThermwindEnsemble, TwoColEnsemble, JN2018Ensemble,
                         JN2018ImplicitEnsemble, TwoBasinEnsemble, TwoBasinSweep)
 from .forcing import ForcingSchedule
+from .noise import NoiseForcing
 from .indices import RowIndices, IndexRecorder
 from . import diagnostics
 from . import plotting

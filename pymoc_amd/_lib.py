@@ -275,6 +275,24 @@ class pm_forcing(C.Structure):
               ("target", pm_forcing_target * PM_FORCING_MAX_TARGETS)]
 
 
+PM_NOISE_MAX_TARGETS, PM_NOISE_STREAMS = 8, 6
+
+
+class pm_noise_target(C.Structure):
+  """Mirror of `struct pm_noise_target` (include/pymoc_hip.h)."""
+  _fields_ = [("dst", c_dp), ("row0", C.c_int64), ("base", c_dp), ("pattern", c_dp),
+              ("sigma", c_dp), ("x_in", c_dp), ("x_out", c_dp), ("xi_out", c_dp),
+              ("a", C.c_double), ("b", C.c_double), ("len", C.c_int32),
+              ("pattern_per_member", C.c_int32), ("stream", C.c_int32), ("reserved", C.c_int32)]
+
+
+class pm_noise(C.Structure):
+  """Mirror of `struct pm_noise` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("ntargets", C.c_int32), ("j", C.c_uint32),
+              ("reserved", C.c_uint32), ("seed", C.c_uint64), ("member0", C.c_int64),
+              ("target", pm_noise_target * PM_NOISE_MAX_TARGETS)]
+
+
 PM_INDICES_MAX = 32
 PM_IDX_MAX, PM_IDX_MIN, PM_IDX_AT, PM_IDX_CROSS, PM_IDX_MEAN = 0, 1, 2, 3, 4
 
@@ -395,6 +413,7 @@ SIGNATURES = {
     "pm_steady_check": (C.c_int, [C.POINTER(pm_steady_check), C.c_void_p]),
     "pm_forcing_apply": (C.c_int, [C.POINTER(pm_forcing), C.c_double, C.c_void_p]),
     "pm_row_indices": (C.c_int, [C.POINTER(pm_row_indices), c_dp, c_dp, C.c_void_p]),
+    "pm_forcing_noise": (C.c_int, [C.POINTER(pm_noise), C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

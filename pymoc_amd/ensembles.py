@@ -22,8 +22,9 @@ from ._lib import check, lib
 from .columns import ColumnBatch, _HINT_DIV3_OFF, check_scheme, div3_licensed
 from .device import DeviceArray, Event, Graph, Stream, _sh, launch_span
 from .equilibrium import ColumnEquiBatch
+from .noise import application as noise_application
 from .psi_so import PsiSOBatch
-from .sharding import DiagnosticGather
+from .sharding import DiagnosticGather, member_range
 from .so_ml import SOMLBatch
 from .thermwind import ThermwindBatch
 
@@ -178,6 +179,7 @@ class CoupledEnsemble(object):
   # optional indices.IndexRecorder (it attaches itself): sampled at the `_gather_if_due` sites,
   # right after the overturning update at that step; None: no launch is added anywhere
   indices = None
+  _noise = None  # the BoundNoise of `noise=`, where a driver takes one
 
   @classmethod
   def members(cls, cfg):
@@ -235,31 +237,63 @@ class CoupledEnsemble(object):
         out[name] = np.asarray(cfg['y']).size if profile else 1
     return out
 
-  def _check_forcing(self, forcing, cfg, n, **excluded):
-    """A constructor's first act, before any device state: refuse what a schedule cannot go with,
-    and the schedule's names and shapes against this cfg."""
+  def _check_forcing(self, forcing, cfg, n, noise=None, comm=None, n_total=None, **excluded):
+    """A constructor's first act, before any device state: refuse what a schedule or a
+    NoiseForcing cannot go with, and their names and shapes against this cfg.  `comm`, `n_total`:
+    the shard this rank holds -- the noise counts members by their global index."""
     self._forcing, self._forced_at = None, -1
-    if forcing is None:
-      return
-    for kw, on in excluded.items():
-      if on:
-        raise ValueError("forcing does not go with %s=True: a captured or persistent launch "
-                         "spans the steps the schedule is applied at" % kw)
-    forcing.check(self.forcing_lengths(cfg, n), n)
+    self._noise, self._noise_spec = None, noise
+    for what, given in (("forcing", forcing), ("noise", noise)):
+      if given is None:
+        continue
+      for kw, on in excluded.items():
+        if on:
+          raise ValueError("%s does not go with %s=True: a captured or persistent launch "
+                           "spans the steps the schedule is applied at" % (what, kw))
+      given.check(self.forcing_lengths(cfg, n), n)
+    self._member0 = 0
+    if noise is not None and comm is not None:
+      self._member0 = member_range(n if n_total is None else n_total, comm.world, comm.rank)[0]
+
+  @property
+  def noise(self):
+    """The BoundNoise of `noise=NoiseForcing(...)` (its get_state / set_state carry the noise
+    states across runs); None without one."""
+    return self._noise
 
   def _bind_forcing(self, forcing, cfg):
     """A constructor's last act ahead of its own first update (which uses the cfg's values)."""
+    n, lengths = self.n, self.forcing_lengths(cfg, self.n)
+
+    def destinations(names):
+      targets = {}
+      for name in names:
+        targets[name] = []
+        for path, group, _ in self.FORCING_TARGETS[name]:
+          a = self
+          for attr in path.split("."):
+            a = getattr(a, attr)
+          targets[name].append((a, group * n, lengths[name]))
+      return targets
+
+    noise = self._noise_spec
+    if noise is not None:
+      # the noise keeps a copy of the cfg's values as its base and writes every real destination;
+      # a schedule on the same target writes that base instead (once, whatever the destinations)
+      self._noise = noise.bind(n, destinations(noise.targets), member0=self._member0,
+                               stream=self.stream)
+      # a Gaussian deviate has no bound: the columns test every bs operand (bit-identical
+      # results), as under a schedule with knots outside the window below
+      if "bs" in noise.targets or "bs_north" in noise.targets:
+        self.cols._par_ok["bs"] = np.zeros(self.cols.ncols, dtype=bool)
+        self.cols._upload_flags()
     if forcing is None:
       return
-    n, lengths = self.n, self.forcing_lengths(cfg, self.n)
-    targets = {}
-    for name in forcing.values:
-      targets[name] = []
-      for path, group, _ in self.FORCING_TARGETS[name]:
-        a = self
-        for attr in path.split("."):
-          a = getattr(a, attr)
-        targets[name].append((a, group * n, lengths[name]))
+    targets = destinations(forcing.values)
+    if self._noise is not None:
+      for name in targets:
+        if name in self._noise.base:
+          targets[name] = [(self._noise.base[name], 0, lengths[name])]
     self._forcing = forcing.bind(n, targets, stream=self.stream)
     # PM_COL_STATIC_IN_RANGE was derived from the cfg's bs; it stays only where every value the
     # schedule can write is zero or inside the exact-division window [2^-200, 2^200]: knots that
@@ -279,12 +313,18 @@ class CoupledEnsemble(object):
     reference user loop that assigns at the top of the loop body puts it: ahead of the MOC update
     of iteration s for JN2018Ensemble, behind the update that follows step s - 1 for
     TwoColEnsemble."""
-    if self._forcing is None or self._forced_at == self.ii:
+    if (self._forcing is None and self._noise is None) or self._forced_at == self.ii:
       return
     s = self.ii
     if s == 0 or s % self.M == self.RESTART_PHASE % self.M:
-      with launch_span(self.timer, "k_forcing_apply", self.stream):
-        self._forcing.apply(s * self.dt, self.stream)
+      if self._forcing is not None:
+        with launch_span(self.timer, "k_forcing_apply", self.stream):
+          self._forcing.apply(s * self.dt, self.stream)
+      if self._noise is not None:
+        # right behind the schedule's launch, which wrote the base of the targets they share
+        j, elapsed = noise_application(s, self.M, self.RESTART_PHASE, self.dt)
+        with launch_span(self.timer, "k_forcing_noise", self.stream):
+          self._noise.apply(j, elapsed, self.stream)
       self._forced_at = s
 
   @staticmethod
@@ -395,7 +435,7 @@ class TwoColEnsemble(CoupledEnsemble):
   def __init__(self, cfg, stream=None, lanes_per_col=0, comm=None, n_total=None,
                diag_iters=None, keep_history=False, arith="exact", overlap_updates=False,
                fused_run=None, gather="all", gather_overlap=True, forcing=None,
-               scheme="explicit"):
+               scheme="explicit", noise=None):
     """`scheme="implicit"`: the columns step with backward Euler (ColumnBatch.steps(scheme=
     "implicit"), pm_column_steps_implicit) -- stable at any dt, an extension with no reference
     counterpart (a tolerance path); the forcing reaches them as an array (the thermal wind's wA
@@ -424,11 +464,15 @@ class TwoColEnsemble(CoupledEnsemble):
     `arith="contracted"`: the columns step in the opt-in tolerance mode (ColumnBatch.steps).
     `forcing`: a ForcingSchedule for bs, bs_north and, with an SO channel, tau (in the form of the
     batch's tau: one value per member or a profile on y) and bs_SO, applied by the rule of
-    `_apply_forcing`; the constructor's own update uses the cfg's values.  Not with fused_run."""
+    `_apply_forcing`; the constructor's own update uses the cfg's values.  Not with fused_run.
+    `noise`: a NoiseForcing on the same targets, applied at the same instants right behind the
+    schedule (pymoc_amd.noise); with `comm`, members are counted by their global index.  Not with
+    fused_run."""
     z = cfg['z']
     nz = z.size
     n = self.members(cfg)
-    self._check_forcing(forcing, cfg, n, fused_run=fused_run)
+    self._check_forcing(forcing, cfg, n, noise=noise, comm=comm, n_total=n_total,
+                        fused_run=fused_run)
     check_scheme(scheme, arith=arith, lanes_per_col=lanes_per_col)
     if scheme == "implicit" and fused_run:
       raise ValueError("scheme='implicit' excludes fused_run")
@@ -615,7 +659,7 @@ class JN2018Ensemble(CoupledEnsemble):
   def __init__(self, cfg, stream=None, lanes_per_col=0, use_graph=False, fused=None,
                comm=None, n_total=None, diag_iters=None, keep_history=False, arith="exact",
                shared_coef=True, fused_run=None, gather="all", gather_overlap=True,
-               split_lanes=False, forcing=None):
+               split_lanes=False, forcing=None, noise=None):
     """`fused_run`: whole stretches of the loop -- many [PsiSO.solve, AMOC.solve / Psibz,
     MOC_up_iters steps] intervals -- in ONE launch of the persistent per-member kernel
     (pm_jn2018_run), ending a launch only where diagnostics are sampled or gathered;
@@ -633,8 +677,13 @@ class JN2018Ensemble(CoupledEnsemble):
     wavefront (PM_JN_SPLIT_LANES; bit-identical; measured a tie on config 5, hence opt-in).
     `forcing`: a ForcingSchedule for bs, bs_north, tau (in the form of the batch's tau), b_rest
     and surflux, applied by the rule of `_apply_forcing` -- ahead of the MOC update of the step,
-    in run() on every path and in moc_update().  Not with use_graph or fused_run."""
-    self._check_forcing(forcing, cfg, self.members(cfg), use_graph=use_graph, fused_run=fused_run)
+    in run() on every path and in moc_update().  Not with use_graph or fused_run.
+    `noise`: a NoiseForcing on the same targets, applied at the same instants right behind the
+    schedule (pymoc_amd.noise).  Not with use_graph or fused_run: base + x * pattern replaces the
+    cfg's values at every application even where sigma is zero, so no captured block is replayed
+    while noise is attached."""
+    self._check_forcing(forcing, cfg, self.members(cfg), noise=noise, comm=comm, n_total=n_total,
+                        use_graph=use_graph, fused_run=fused_run)
     self.arith = self._check_arith(arith)
     self.shared_coef = bool(shared_coef)
     self.split_lanes = bool(split_lanes)
@@ -880,7 +929,7 @@ class JN2018ImplicitEnsemble(JN2018Ensemble):
   arith, shared_coef, fused_run, split_lanes) are not accepted."""
 
   def __init__(self, cfg, stream=None, fused=None, comm=None, n_total=None, diag_iters=None,
-               keep_history=False, gather="all", gather_overlap=True, forcing=None):
+               keep_history=False, gather="all", gather_overlap=True, forcing=None, noise=None):
     """`fused`: None = the fused kernel where it applies (nz <= 256), else one step at a time
     (pm_jn2018_bc_switch, pm_column_steps_implicit, pm_so_ml_step); False forces the latter;
     True where the kernel does not apply is a ValueError.  The two are bit-identical.  The other
@@ -889,7 +938,7 @@ class JN2018ImplicitEnsemble(JN2018Ensemble):
       raise ValueError("fused=True needs nz <= 256 (nz=%d)" % cfg['z'].size)
     JN2018Ensemble.__init__(self, cfg, stream=stream, fused=fused, comm=comm, n_total=n_total,
                             diag_iters=diag_iters, keep_history=keep_history, gather=gather,
-                            gather_overlap=gather_overlap, forcing=forcing)
+                            gather_overlap=gather_overlap, forcing=forcing, noise=noise)
 
   def _step(self):
     check(lib.pm_jn2018_bc_switch(C.byref(self._bc), _sh(self.stream)))
@@ -1101,9 +1150,10 @@ class TwoBasinSweep(TwoBasinEnsemble):
   `forcing`: bs (the Atlantic and Pacific columns share it, :41-47: two destinations), bs_north,
   tau (both sectors' Psi_SO: two destinations) and bs_SO (the one array both sectors read), applied
   by the rule of `_apply_forcing`: at s = 0 and s = 1 (mod MOC_up_iters), ahead of the steps;
-  the constructor's own update uses the cfg's values.  While a schedule is bound the loop runs
-  launch by launch: no hipGraph is captured (`use_graph` with `overlap_updates` is the slower
-  option anyway, see the parent's constructor).
+  the constructor's own update uses the cfg's values.  `noise=NoiseForcing(...)` perturbs the same
+  targets at the same instants (bs and tau: one noise state for both destinations).  While a
+  schedule or a noise is bound the loop runs launch by launch: no hipGraph is captured
+  (`use_graph` with `overlap_updates` is the slower option anyway, see the parent's constructor).
 
   `scheme="implicit"`: the three column groups step with backward Euler (pm_twobasin_forcing and
   pm_column_steps_implicit on the array -- the default, measured no slower -- or
@@ -1131,9 +1181,9 @@ class TwoBasinSweep(TwoBasinEnsemble):
   def __init__(self, cfg, stream=None, lanes_per_col=0, comm=None, n_total=None,
                diag_iters=None, keep_history=False, arith="exact", overlap_updates=False,
                gather="all", gather_overlap=True, use_graph=True, forcing=None,
-               scheme="explicit"):
+               scheme="explicit", noise=None):
     n = self.members(cfg)
-    self._check_forcing(forcing, cfg, n)
+    self._check_forcing(forcing, cfg, n, noise=noise, comm=comm, n_total=n_total)
     check_scheme(scheme, arith=arith, lanes_per_col=lanes_per_col)
     self.scheme = scheme
     # every per-member key as an explicit [n, ...] array by its rule: the parent's own reading of
@@ -1178,7 +1228,7 @@ class TwoBasinSweep(TwoBasinEnsemble):
     return "k_column_steps" if n >= 3 else "k_column_steps_short"
 
   def run(self, nsteps):
-    if self._forcing is None and self.scheme == "explicit":
+    if self._forcing is None and self._noise is None and self.scheme == "explicit":
       return TwoBasinEnsemble.run(self, nsteps)
     remaining = int(nsteps)
     while remaining > 0:

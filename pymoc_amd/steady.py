@@ -75,6 +75,9 @@ def _validate(cls, cfg, kw, check_every):
   if kw.get("forcing") is not None:
     raise ValueError("run_to_steady does not take forcing: an ensemble under a time-dependent "
                      "schedule has no steady state to run to")
+  if kw.get("noise") is not None:
+    raise ValueError("run_to_steady does not take noise: an ensemble under a time-dependent "
+                     "schedule has no steady state to run to")
   if kw.get("comm") is not None or kw.get("keep_history"):
     raise ValueError("run_to_steady does not take comm or keep_history: call it per rank and "
                      "gather the results")
@@ -205,7 +208,7 @@ def run_to_steady(cls, cfg, tol, max_steps, check_every=None, consecutive=1, com
   compact_below rebuild the ensemble from its running members once at most this share of the rows
                 is still running (0: never, 1: at every check that retired a member)
 Returns a SteadyResult.  Refused (ValueError): other classes, arith != 'exact', fused_run, comm,
-keep_history, forcing (a ForcingSchedule), a check_every that is not a multiple of MOC_up_iters."""
+keep_history, forcing (a ForcingSchedule), noise (a NoiseForcing), a check_every that is not a multiple of MOC_up_iters."""
   M, check_every = _validate(cls, cfg, ensemble_kwargs, check_every)
   s0, checks = check_schedule(cls, M, check_every, max_steps)
   if int(consecutive) < 1:
