@@ -808,7 +808,7 @@ __global__ __launch_bounds__(64 * ML_WAVES_PER_BLOCK, 2) void k_jn2018_steps(pm_
       bad |= !isfinite(v);
       if (m_ok) {
         a.ml.bs[by + j] = v;
-        if (a.ml.Psi_s) a.ml.Psi_s[by + j] = w.ps[j];
+        if (a.ml.Psi_s && ps_valid) a.ml.Psi_s[by + j] = w.ps[j];  // (w.ps is unset until a step ran)
       }
     }
   }

@@ -782,16 +782,19 @@ class JN2018Ensemble(CoupledEnsemble):
 
   def _div3(self):
     """PM_JN_DIV3_PROVEN: the columns' static denominators (ColumnBatch.div3_proven) and the
-    mixed layer's h, L and y[1] - y[0] admit the 3-instruction exact quotient."""
-    if not hasattr(self, "_div3_ok"):
-      t = self.ml
-      den = np.array([t.h, t.L, t.y_host[1] - t.y_host[0]], dtype=np.float64)
-      a = np.abs(den)
-      self._div3_ok = bool(self.cols.uniform_area and self.cols.div3_proven and
-                           not (self.cols.__dict__.get("_hints_off", 0) & _HINT_DIV3_OFF) and
-                           ((a >= 2.0**-200) & (a <= 2.0**200)).all() and
-                           div3_licensed(den))
-    return self._div3_ok
+    mixed layer's h, L and y[1] - y[0] admit the 3-instruction exact quotient.  Decided per
+    descriptor from the columns' present state -- `cols.set_static` re-derives their proof and
+    `cols.use_hints(div3=False)` withdraws it -- only the mixed layer's part is kept, for as long
+    as its three denominators stay what they were."""
+    t = self.ml
+    den = (float(t.h), float(t.L), float(t.y_host[1] - t.y_host[0]))
+    if getattr(self, "_ml_div3", (None, False))[0] != den:
+      a = np.abs(np.array(den, dtype=np.float64))
+      self._ml_div3 = (den, bool(((a >= 2.0**-200) & (a <= 2.0**200)).all() and
+                                 div3_licensed(np.array(den, dtype=np.float64))))
+    c = self.cols
+    return bool(c.uniform_area and c.div3_proven and
+                not (c.__dict__.get("_hints_off", 0) & _HINT_DIV3_OFF) and self._ml_div3[1])
 
   def _jn_descriptor(self):
     d = _lib.pm_jn2018()

@@ -39,8 +39,12 @@ GPU_TOL_FACTOR = I.GPU_TOL_FACTOR  # DESIGN.md section 13's argument: up to 8 el
 TIE_MARGIN = 1e-6
 
 
-def make_case(name, nz, ny, n, r=0.77, area="const", kind0=0, dt_days=30.0):
-  """n members of kinds kind0, kind0 + 1, ... (mod KINDS).  r = max(kappa) dt / dz^2."""
+def make_case(name, nz, ny, n, r=0.77, area="const", kind0=0, dt_days=30.0, shared=False,
+              ksel0=None, kappaeff_entries=None, Psi_SO_rows=None, bs_SO0_south=None):
+  """n members of kinds kind0, kind0 + 1, ... (mod KINDS).  r = max(kappa) dt / dz^2.
+  shared: every member gets member 0's kappa, kappaeff and Area rows (PM_JN_SHARED_COEF).
+  Per-member overrides, each a dict: ksel0 {column: set}, kappaeff_entries {(member, level):
+  value}, Psi_SO_rows {member: row [nz]} (wA follows), bs_SO0_south {member: bs_SO0[member, 0]}."""
   H = 4000.0
   z = np.linspace(-H, 0.0, nz)
   y = np.linspace(0.0, 2.0e6, ny)
@@ -48,12 +52,15 @@ def make_case(name, nz, ny, n, r=0.77, area="const", kind0=0, dt_days=30.0):
   dz = z[1] - z[0]
   kinds = (kind0 + np.arange(n)) % KINDS
   m = np.arange(n)
+  mc = np.zeros(n, dtype=m.dtype) if shared else m  # whose coefficients a member takes
   shape = 1.0 + 2.0 * np.exp(z / 800.0)                        # max 3 at the surface
-  kbase = r * dz * dz / (3.0 * dt) * (1.0 - 0.05 * (m % 3))   # max over members: r exactly-ish
+  kbase = r * dz * dz / (3.0 * dt) * (1.0 - 0.05 * (mc % 3))  # max over members: r exactly-ish
   kap = kbase[:, None] * shape[None, :]
   taper = 0.2 + 0.8 * np.minimum(1.0, (z + H) / 1200.0)        # bottom boundary layer
   kapeff = kap * taper[None, :]
-  A_b = 8e13 * (1.0 + 0.1 * (m % 2))
+  for (mm, lev), v in (kappaeff_entries or {}).items():
+    kapeff[mm, lev] = v
+  A_b = 8e13 * (1.0 + 0.1 * (mc % 2))
   A_n = A_b / 50.0
   if area == "const":
     prof = np.ones(nz)
@@ -68,6 +75,8 @@ def make_case(name, nz, ny, n, r=0.77, area="const", kind0=0, dt_days=30.0):
   Psi_SO = 2.0 * sinp[None, :] * (1.0 + 0.1 * m[:, None])
   Psi_SO[:, 0] = 0.0
   Psi_SO[:, 1] = np.where(south, -0.4, 0.5)
+  for mm, row in (Psi_SO_rows or {}).items():
+    Psi_SO[mm] = row
   Pb = 1.5 * sinp[None, :] * np.ones((n, 1))
   Pb[:, 1] = np.where(np.isin(kinds, (1, 2, 3, 4)), 0.3, -0.2)
   Pn = 1.0 * sinp[None, :] * np.ones((n, 1))
@@ -98,15 +107,20 @@ def make_case(name, nz, ny, n, r=0.77, area="const", kind0=0, dt_days=30.0):
                     / alpha + bs0[:, None])
   bs_SO = b_rest.copy()
   bs_SO[:, -1] = bs
+  for mm, v in (bs_SO0_south or {}).items():
+    bs_SO[mm, 0] = v
   surflux = np.zeros((n, ny))
   surflux[:, 1:j6] = -(5.9e3 / 4e6 / 2e5) * (1.0 + 0.2 * m[:, None])
   rest_mask = np.zeros((n, ny))
   rest_mask[:, j6:-1] = 1.0
+  sel0 = np.ones(2 * n, dtype=np.int32)
+  for col, v in (ksel0 or {}).items():
+    sel0[col] = v
   return dict(name=name, nz=nz, ny=ny, n=n, z=z, y=y, dt=dt, r=r, kinds=kinds, kappa=kap,
               kappaeff=kapeff, area=area_rows, b0=b0, bs=np.concatenate([bs, bs_north]),
               N2min=np.full(2 * n, 1e-7), Psi_SO=Psi_SO, Psi_res_b=Pb, Psi_res_n=Pn, wA=wA,
               bs_SO0=bs_SO, surflux=surflux, rest_mask=rest_mask, b_rest=b_rest, Ks=400.0, h=50.0,
-              L=4e6, v_pist=1.5 / DAY, bbot0=b0[:, 0].copy(), ksel0=np.ones(2 * n, dtype=np.int32))
+              L=4e6, v_pist=1.5 / DAY, bbot0=b0[:, 0].copy(), ksel0=sel0)
 
 
 # name, nz, ny, n, keywords.  nz: both sides of every levels-per-lane boundary (64 | 65, 128 | 129,

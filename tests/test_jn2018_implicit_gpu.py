@@ -8,107 +8,10 @@ import numpy as np
 import pytest
 
 import jn2018_implicit_cases as J
+from jn2018_members import OUTPUTS, Members
 
 pytestmark = pytest.mark.gpu
 TOL = J.GPU_TOL_FACTOR * J.E_COUPLED
-SENTINEL = -7.25e300
-OUTPUTS = ("b", "bs_SO", "Psi_s", "bbot", "ksel", "nonfinite", "status")
-
-
-class Members(object):
-  """A case on the device.  Every array a launch writes sits inside an arena with one guard
-  member (row) before and after it, filled with a sentinel."""
-
-  def __init__(self, gpu, case):
-    from pymoc_amd import _lib
-    from pymoc_amd.device import DeviceArray
-    self.case, self.n = case, case["n"]
-    n, nz, ny = case["n"], case["nz"], case["ny"]
-    two = lambda a: np.concatenate([a, a])  # noqa: E731
-    self.cols = gpu.ColumnBatch(case["z"], two(case["kappa"]), case["area"], case["b0"],
-                                bs=case["bs"], bbot=case["bbot0"], N2min=case["N2min"],
-                                do_conv=True, kappa_alt=two(case["kappaeff"]))
-    self.ml = gpu.SOMLBatch(case["y"], nz, case["bs_SO0"], surflux=case["surflux"],
-                            rest_mask=case["rest_mask"], b_rest=case["b_rest"], Ks=case["Ks"],
-                            h=case["h"], L=case["L"], v_pist=case["v_pist"])
-    self.arenas = {}
-
-    def arena(name, rows, length, dtype=np.float64):
-      host = np.full((rows + 2, length), SENTINEL if dtype == np.float64 else -77, dtype=dtype)
-      a = DeviceArray.from_host(host)
-      self.arenas[name] = (a, host, rows)
-      return a.view(1, rows)
-
-    self.cols.b = arena("b", 2 * n, nz)
-    self.ml.bs = arena("bs_SO", n, ny)
-    self.ml.Psi_s = arena("Psi_s", n, ny)
-    # (per-column scalars: the guard "member" is one element)
-    self.cols.bbot = arena("bbot", 2 * n, 1)
-    self.cols.ksel = arena("ksel", 2 * n, 1, np.int32)
-    self.cols.nonfinite = arena("nonfinite", 2 * n, 1, np.int32)
-    self.ml.status = arena("status", n, 1, np.int32)
-    self.wA = DeviceArray.from_host(case["wA"])
-    self.Psi_SO = DeviceArray.from_host(case["Psi_SO"])
-    self.Pb = DeviceArray.from_host(case["Psi_res_b"])
-    self.Pn = DeviceArray.from_host(case["Psi_res_n"])
-    self.b_basin, self.b_north = self.cols.b.view(0, n), self.cols.b.view(n, n)
-    self.reset()
-    bc = self.bc = _lib.pm_jn2018_bc()
-    bc.n, bc.nz, bc.ny, bc.reserved = n, nz, ny, 0
-    bc.Psi_SO, bc.Psi_res_b, bc.Psi_res_n = self.Psi_SO.ptr, self.Pb.ptr, self.Pn.ptr
-    bc.b_basin, bc.b_north, bc.bs_SO = self.b_basin.ptr, self.b_north.ptr, self.ml.bs.ptr
-    bc.bbot, bc.ksel = self.cols.bbot.ptr, self.cols.ksel.ptr
-
-  def reset(self):
-    c, n = self.case, self.n
-    self.cols.b.upload(c["b0"])
-    self.ml.bs.upload(c["bs_SO0"])
-    self.ml.Psi_s.upload(np.zeros((n, c["ny"])))
-    self.cols.bbot.upload(c["bbot0"].reshape(-1, 1))
-    self.cols.ksel.upload(c["ksel0"].reshape(-1, 1))
-    self.cols.nonfinite.upload(np.full((2 * n, 1), 5, dtype=np.int32))
-    self.ml.status.upload(np.full((n, 1), 5, dtype=np.int32))
-
-  def descriptor(self, hints=0):
-    from pymoc_amd import _lib
-    d = _lib.pm_jn2018()
-    d.n, d.hints = self.n, hints
-    d.cols = self.cols.descriptor()
-    d.wA, d.Psi_SO, d.Psi_res_b, d.Psi_res_n = self.wA.ptr, self.Psi_SO.ptr, self.Pb.ptr, self.Pn.ptr
-    ml, t = _lib.pm_so_ml(), self.ml
-    ml.n, ml.nz, ml.ny, ml.reserved = t.n, t.nz, t.ny, 0
-    ml.y, ml.bs, ml.Psi_s = t.y.ptr, t.bs.ptr, t.Psi_s.ptr
-    ml.b_basin, ml.Psi_b = None, None
-    ml.surflux, ml.rest_mask, ml.b_rest = t.surflux.ptr, t.rest_mask.ptr, t.b_rest.ptr
-    ml.Ks, ml.h, ml.L, ml.v_pist = t.Ks, t.h, t.L, t.v_pist
-    ml.status = t.status.ptr
-    d.ml = ml
-    return d
-
-  def fused(self, nsteps, dt=None, hints=0):
-    from pymoc_amd._lib import lib
-    d = self.descriptor(hints)
-    return lib.pm_jn2018_steps_implicit(C.byref(d), self.case["dt"] if dt is None else dt,
-                                        int(nsteps), None)
-
-  def sequence(self, nsteps):
-    from pymoc_amd._lib import check, lib
-    for _ in range(nsteps):
-      check(lib.pm_jn2018_bc_switch(C.byref(self.bc), None))
-      self.cols.steps(self.wA, self.case["dt"], 1, scheme="implicit")
-      self.ml.step(self.b_basin, self.Psi_SO, self.case["dt"])
-
-  def outputs(self):
-    """name -> the launch's own rows; asserts that the guard rows still hold the sentinel."""
-    out = {}
-    for name, (a, host, rows) in self.arenas.items():
-      got = a.download()
-      for g in (0, rows + 1):
-        assert got[g].tobytes() == host[g].tobytes(), "guard row of %s overwritten" % name
-      out[name] = got[1:rows + 1]
-    return out
-
-
 _members = {}
 
 
@@ -116,7 +19,7 @@ _members = {}
 def members(gpu):
   def get(name):
     if name not in _members:
-      _members[name] = Members(gpu, J.get_case(name))
+      _members[name] = Members(gpu, J.get_case(name), "pm_jn2018_steps_implicit")
     _members[name].reset()
     return _members[name]
   return get
@@ -137,7 +40,7 @@ def test_fused_equals_the_launch_sequence_bitwise(gpu, members, name):
     _lib.check(m.fused(k))
     got = m.outputs()
     m.reset()
-    m.sequence(k)
+    m.sequence(k, "implicit")
     want = m.outputs()
     _bitwise(got, want, (name, k))
     assert np.isfinite(got["b"]).all() and np.isfinite(got["bs_SO"]).all()
