@@ -1178,6 +1178,97 @@ struct pm_noise {
 /* the struct is named by its tag only, as pm_steady_check's is */
 int pm_forcing_noise(const struct pm_noise *d, pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Statistics of a recorded series (pymoc_amd.SeriesStats), reduced on the device: ONE launch per
+ * entry.  (no counterpart: what a user computes in NumPy from the downloaded series.)  Both entries
+ * read a series of doubles
+ *   v[k][s][m],  k < nrec records, s < nspec indices, m < n members (members contiguous: an
+ *   IndexRecorder's device layout)
+ * over the record window [k0, k1).  A value is FINITE iff isfinite; non-finite values mark members
+ * that blew up: they are excluded and counted, never propagated.  Every sum below has one order,
+ * which is part of the ABI: it does not depend on the kernel variant, the block size or the launch
+ * geometry, and with every product and sum rounded on its own (-ffp-contract=off) each double is
+ * reproduced bit for bit by a NumPy restatement.
+ *
+ * pm_series_group_stats -- across the members of a group, per (record k in the window, index s,
+ * group g):
+ *   count[k][s][g]            (int32)
+ *   stat[k][s][g][5 + nq]     mean, var, min, max, sum, q_0 .. q_{nq-1}
+ * (both [nrec][nspec][ngroups]; records outside the window are not touched).  order[n] is a
+ * permutation of the members sorted by group, ascending member index inside a group; group g is
+ * order[start[g] .. start[g+1] - 1].  For the group's values x_0 .. x_{G-1} in that order:
+ *   count   the number of finite x_j;  x'_j = x_j if x_j is finite, else +0.0
+ *   sum     p[l], l < 64, is the sequential sum in ascending j of the x'_j with j = l (mod 64),
+ *           starting from +0.0; then for stride = 32, 16, 8, 4, 2, 1: p[l] += p[l + stride] for
+ *           l < stride; sum = p[0]
+ *   mean    sum / count
+ *   var     Q / (count - 1), Q the same tree over d_j * d_j with d_j = x_j - mean for finite x_j
+ *           and 0 otherwise; NaN for count < 2
+ *   min, max  the first and the last of the finite values sorted ascending, -0.0 before +0.0: the
+ *           very bits
+ *   q_i     NumPy's method="linear" on the sorted finite values: m = count, vi = q * (m - 1),
+ *           lo = floor(vi), hi = min(lo + 1, m - 1), g = vi - lo, a = sorted[lo], b = sorted[hi];
+ *           g >= 0.5 ? b - (b - a) * (1 - g) : a + (b - a) * g
+ *   count = 0 stores NaN in every double of stat.  A group of size 0 is allowed (count 0).
+ * Groups of at most 64 members are reduced by one wavefront in registers, larger ones (at most
+ * PM_STATS_GROUP_MAX, sorted in 64 KiB of LDS) by a workgroup; sizes may differ within a launch,
+ * and every value of the window is read once.
+ *
+ * pm_series_member_stats -- along the records, per (index s, member m):
+ *   count[s][m], first[s][m], ncross[s][m]   (int32)
+ *   stat[s][m][6 + nlag]                     mean, var, min, max, sum, frac, c_{L_0} ..
+ * The records of the window are cut into chunks of PM_STATS_CHUNK consecutive records counted from
+ * k0.  A chunk's partial is the sequential sum in ascending k of its terms, starting from +0.0; a
+ * total is the sequential sum of the chunk partials in ascending order, starting from +0.0.
+ *   count   the number of finite records;  sum: the total of x'_k (x_k if finite, else +0.0)
+ *   mean    sum / count;  var = Q / (count - 1), Q the total of d_k * d_k, d_k = x_k - mean for
+ *           finite x_k and 0 otherwise; NaN for count < 2
+ *   min, max  over the finite records; of -0.0 and +0.0, min takes -0.0 and max +0.0
+ *   c_L     the total, over the k with x_k and x_{k+L} both finite and both inside the window, of
+ *           (x_k - mean) * (x_{k+L} - mean) (other k contribute +0.0; a pair belongs to the chunk
+ *           of k), divided by the number of such pairs; NaN with no such pair
+ *   thr[s] = t (NaN: none), dir[s] = d: x_k is a HIT iff it is finite and x_k < t (d = -1) or
+ *           x_k > t (d = +1).  frac = hits / count; first = the smallest hit k (an absolute record
+ *           number), -1 if none; ncross = the number of k with x_k and x_{k+1} both finite, both
+ *           inside the window, and exactly one of them a hit.  Without a threshold: NaN, -1, 0
+ *   count = 0 stores NaN in mean, var, min, max (and frac), and sum = +0.0.
+ *
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): no NULL pointer where one is
+ * read or written (q / lag may be NULL with nq / nlag = 0); n, nspec, nrec >= 1 (nspec <= 65535,
+ * (k1 - k0) * nspec < 2^30); 0 <= k0 < k1 <= nrec; ngroups >= 1; 0 <= nq <= PM_STATS_Q_MAX,
+ * every q in [0, 1] and not NaN; 0 <= nlag <= PM_STATS_LAG_MAX, every L in [1, k1 - k0); dir -1 or
+ * +1; start[0] = 0, start monotone, start[ngroups] = n, no group larger than PM_STATS_GROUP_MAX.
+ * The checks read the HOST mirrors (start, q, lag, thr, dir); the kernels read the device copies
+ * of the same values.  That order is a permutation of 0 .. n-1 is the caller's to ensure.     */
+#define PM_STATS_Q_MAX 8
+#define PM_STATS_LAG_MAX 4
+#define PM_STATS_GROUP_MAX 8192
+#define PM_STATS_CHUNK 256
+struct pm_series_group_stats {
+  int32_t n, nspec, nrec, k0, k1, ngroups, nq, reserved;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  const int32_t *order;                  /* device [n]                                            */
+  const int32_t *start;                  /* HOST [ngroups + 1]                                    */
+  const int32_t *start_dev;              /* DEVICE, the same values                               */
+  const double *q;                       /* HOST [nq]                                             */
+  const double *q_dev;                   /* DEVICE, the same values                               */
+};
+/* the struct is named by its tag only, as pm_steady_check's is */
+int pm_series_group_stats(const struct pm_series_group_stats *d, int32_t *count, double *stat,
+                          pm_stream_t stream);
+struct pm_series_member_stats {
+  int32_t n, nspec, nrec, k0, k1, nlag, reserved1, reserved2;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  const int32_t *lag;                    /* HOST [nlag]                                           */
+  const int32_t *lag_dev;                /* DEVICE, the same values                               */
+  const double *thr;                     /* HOST [nspec]; NaN: no threshold                       */
+  const double *thr_dev;                 /* DEVICE, the same values                               */
+  const int32_t *dir;                    /* HOST [nspec]: -1 below, +1 above                      */
+  const int32_t *dir_dev;                /* DEVICE, the same values                               */
+};
+int pm_series_member_stats(const struct pm_series_member_stats *d, int32_t *count, int32_t *first,
+                           int32_t *ncross, double *stat, pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

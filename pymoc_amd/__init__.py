@@ -26,6 +26,7 @@ from .ensembles import (EquiIterationEnsemble, ColumnThermwindEnsemble, TwoColEn
 from .forcing import ForcingSchedule
 from .noise import NoiseForcing
 from .indices import RowIndices, IndexRecorder
+from .stats import SeriesStats
 from . import diagnostics
 from . import plotting
 from . import steady

@@ -308,6 +308,27 @@ class pm_row_indices(C.Structure):
   _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("spec", C.c_void_p), ("spec_dev", c_dp)]
 
 
+PM_STATS_Q_MAX, PM_STATS_LAG_MAX, PM_STATS_GROUP_MAX, PM_STATS_CHUNK = 8, 4, 8192, 256
+
+
+class pm_series_group_stats(C.Structure):
+  """Mirror of `struct pm_series_group_stats` (include/pymoc_hip.h); `start` and `q` are HOST
+  addresses."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("ngroups", C.c_int32), ("nq", C.c_int32),
+              ("reserved", C.c_int32), ("v", c_dp), ("order", c_dp), ("start", C.c_void_p),
+              ("start_dev", c_dp), ("q", C.c_void_p), ("q_dev", c_dp)]
+
+
+class pm_series_member_stats(C.Structure):
+  """Mirror of `struct pm_series_member_stats` (include/pymoc_hip.h); `lag`, `thr` and `dir` are
+  HOST addresses."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("nlag", C.c_int32), ("reserved1", C.c_int32),
+              ("reserved2", C.c_int32), ("v", c_dp), ("lag", C.c_void_p), ("lag_dev", c_dp),
+              ("thr", C.c_void_p), ("thr_dev", c_dp), ("dir", C.c_void_p), ("dir_dev", c_dp)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -414,6 +435,9 @@ SIGNATURES = {
     "pm_forcing_apply": (C.c_int, [C.POINTER(pm_forcing), C.c_double, C.c_void_p]),
     "pm_row_indices": (C.c_int, [C.POINTER(pm_row_indices), c_dp, c_dp, C.c_void_p]),
     "pm_forcing_noise": (C.c_int, [C.POINTER(pm_noise), C.c_void_p]),
+    "pm_series_group_stats": (C.c_int, [C.POINTER(pm_series_group_stats), c_dp, c_dp, C.c_void_p]),
+    "pm_series_member_stats": (C.c_int, [C.POINTER(pm_series_member_stats), c_dp, c_dp, c_dp, c_dp,
+                                         C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
