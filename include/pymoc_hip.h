@@ -1269,6 +1269,68 @@ struct pm_series_member_stats {
 int pm_series_member_stats(const struct pm_series_member_stats *d, int32_t *count, int32_t *first,
                            int32_t *ncross, double *stat, pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Welch power and cross spectra of a recorded series (pymoc_amd.SeriesSpectra), on the device: ONE
+ * launch.  (no counterpart: what a user computes with scipy.signal.welch / scipy.signal.csd from
+ * the downloaded series.)  The series is v[k][s][m] as above, the record window [k0, k1),
+ * K = k1 - k0, L = nperseg.
+ *   L is a power of two, PM_SPEC_NPERSEG_MIN = 8 <= L <= PM_SPEC_NPERSEG_MAX = 1024;  K >= L
+ *   the step between segments is S = step = L - noverlap, 1 <= S <= L
+ *   segment i, i < nseg = (K - L) / S + 1, holds the records k0 + i*S + j, j < L
+ *   no padding and no partial segment: the records behind the last whole segment are not read
+ * For one series x a segment is USED iff all L of its values are finite (isfinite); the other
+ * segments are excluded and counted, never propagated.  For a used segment:
+ *   1. detrend and window.  PM_SPEC_DETREND_CONSTANT: mu = the sequential sum of x_j in ascending
+ *      j, starting from +0.0, divided by L; y_j = (x_j - mu) * w_j.  PM_SPEC_DETREND_NONE:
+ *      y_j = x_j * w_j.  w[L] is the window the caller passes.
+ *   2. transform.  Z = DFT(y + 0i) with the rounding of the iterative radix-2 decimation-in-time
+ *      transform: a[j] = y[bitrev(j)]; for the stages h = 1, 2, 4 .. L/2, every block base b (a
+ *      multiple of 2h) and every q < h, with W = tw[q * (L / (2h))], u = a[b+q], v = a[b+q+h]:
+ *        tr = W.re*v.re - W.im*v.im      ti = W.re*v.im + W.im*v.re
+ *        a[b+q] = u + (tr, ti)           a[b+q+h] = u - (tr, ti)
+ *      every product and sum rounded on its own (-ffp-contract=off).  tw[j] = (cos(2 pi j / L),
+ *      -sin(2 pi j / L)), j < L/2, is a table the caller passes (twiddle[j][2]: re, im); the
+ *      kernel calls no sin or cos.  (An implementation may fuse stages or skip work on known
+ *      zeros as long as it reproduces these bits.)
+ *   3. periodogram.  p_i[f] = Z.re*Z.re + Z.im*Z.im, f = 0 .. L/2 (nf = L/2 + 1).  For a pair
+ *      (a, b): c_i[f] = conj(Z_a) * Z_b (SciPy's convention),
+ *        re = Za.re*Zb.re + Za.im*Zb.im      im = Za.re*Zb.im - Za.im*Zb.re
+ *      and a pair's segment is used iff it is used for both series.
+ * Results, members contiguous in each:
+ *   nused[s][m], nused_pair[p][m]   (int32) the number of used segments
+ *   psd[f][s][m]                    ((acc[f] / nused) * scale) * c, acc[f] the sequential sum of
+ *                                   p_i[f] over the used segments in ascending i, starting from
+ *                                   +0.0; c = 1 at f = 0 and f = L/2, else 2 (one-sided);
+ *                                   scale = 1 / (fs * sum w^2) is the caller's, one double
+ *   csd[f][2p + {0, 1}][m]          the same of the real and of the imaginary part of c_i[f]
+ * nused = 0 stores NaN.  psd is itself a series [nf][nspec][n] that pm_series_group_stats reads
+ * as it stands.  The result of a series or of a pair depends on that member's values alone: not
+ * on the member's position in the batch, its neighbours, n or the launch geometry.
+ *
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): no NULL pointer where one is
+ * read or written (pair, nused_pair and csd may be NULL iff npairs = 0); n, nspec, nrec >= 1;
+ * 0 <= k0 < k1 <= nrec; L a power of two in [8, 1024]; K >= L; 1 <= step <= L; a known detrend;
+ * 0 <= npairs <= PM_SPEC_PAIRS_MAX, every pair index in [0, nspec); every window value and scale
+ * finite; nf * nspec < 2^30; nspec + npairs <= 65535.  The checks read the HOST mirrors (window,
+ * pair); the kernel reads the device copies of the same values.                              */
+#define PM_SPEC_NPERSEG_MIN 8
+#define PM_SPEC_NPERSEG_MAX 1024
+#define PM_SPEC_PAIRS_MAX 8
+#define PM_SPEC_DETREND_NONE 0
+#define PM_SPEC_DETREND_CONSTANT 1
+struct pm_series_spectra {
+  int32_t n, nspec, nrec, k0, k1, nperseg, step, detrend, npairs, reserved;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  const double *window;                  /* HOST [nperseg]                                        */
+  const double *window_dev;              /* DEVICE, the same values                               */
+  const double *twiddle;                 /* device [nperseg / 2][2]                               */
+  const int32_t *pair;                   /* HOST [npairs][2]                                      */
+  const int32_t *pair_dev;               /* DEVICE, the same values                               */
+  double scale;
+};
+int pm_series_spectra(const struct pm_series_spectra *d, int32_t *nused, double *psd,
+                      int32_t *nused_pair, double *csd, pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

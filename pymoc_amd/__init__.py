@@ -27,6 +27,7 @@ from .forcing import ForcingSchedule
 from .noise import NoiseForcing
 from .indices import RowIndices, IndexRecorder
 from .stats import SeriesStats
+from .spectra import SeriesSpectra
 from . import diagnostics
 from . import plotting
 from . import steady

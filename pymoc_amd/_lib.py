@@ -329,6 +329,20 @@ class pm_series_member_stats(C.Structure):
               ("thr", C.c_void_p), ("thr_dev", c_dp), ("dir", C.c_void_p), ("dir_dev", c_dp)]
 
 
+PM_SPEC_NPERSEG_MIN, PM_SPEC_NPERSEG_MAX, PM_SPEC_PAIRS_MAX = 8, 1024, 8
+PM_SPEC_DETREND_NONE, PM_SPEC_DETREND_CONSTANT = 0, 1
+
+
+class pm_series_spectra(C.Structure):
+  """Mirror of `struct pm_series_spectra` (include/pymoc_hip.h); `window` and `pair` are HOST
+  addresses."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("nperseg", C.c_int32), ("step", C.c_int32),
+              ("detrend", C.c_int32), ("npairs", C.c_int32), ("reserved", C.c_int32),
+              ("v", c_dp), ("window", C.c_void_p), ("window_dev", c_dp), ("twiddle", c_dp),
+              ("pair", C.c_void_p), ("pair_dev", c_dp), ("scale", C.c_double)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -438,6 +452,8 @@ SIGNATURES = {
     "pm_series_group_stats": (C.c_int, [C.POINTER(pm_series_group_stats), c_dp, c_dp, C.c_void_p]),
     "pm_series_member_stats": (C.c_int, [C.POINTER(pm_series_member_stats), c_dp, c_dp, c_dp, c_dp,
                                          C.c_void_p]),
+    "pm_series_spectra": (C.c_int, [C.POINTER(pm_series_spectra), c_dp, c_dp, c_dp, c_dp,
+                                    C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
