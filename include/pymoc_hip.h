@@ -1331,6 +1331,78 @@ struct pm_series_spectra {
 int pm_series_spectra(const struct pm_series_spectra *d, int32_t *nused, double *psd,
                       int32_t *nused_pair, double *csd, pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sliding-window early-warning indicators of a recorded series and the Kendall trend of a series
+ * against its record number (pymoc_amd.SeriesWindows), on the device: ONE launch per entry.  (no
+ * counterpart: what a user computes with a rolling apply over the downloaded series.)  The series
+ * is v[k][s][m] as above, the record window [k0, k1), K = k1 - k0.
+ *
+ * pm_series_windows -- W = window, S = step, Lg = lag:
+ *   PM_WIN_MIN = 4 <= W <= PM_WIN_MAX = 4096 (any W, not only powers of two);  K >= W
+ *   1 <= S <= W;  1 <= Lg <= W - 2
+ *   window i, i < nwin = (K - W) / S + 1, holds the records k0 + i*S + j, j < W
+ *   no partial window: the records behind the last whole window are not read
+ * For one series x a window is USED iff all W of its values are finite (isfinite); the other
+ * windows are excluded and counted, never propagated.  For a used window, every product and sum
+ * rounded on its own (-ffp-contract=off), every sum sequential in ascending j from +0.0:
+ *   t_j   = (double)j - 0.5 * (W - 1)                                  (exact)
+ *   stt   = sum t_j^2 = W (W^2 - 1) / 12, one double the caller passes; the entry checks it against
+ *           its own evaluation
+ *   pass 1  s = sum x_j;  st = sum t_j * x_j
+ *   mean  = s / W
+ *   slope = st / stt for PM_WIN_DETREND_LINEAR; +0.0 for _CONSTANT and _NONE
+ *   r_j   = (x_j - mean) - slope * t_j   LINEAR
+ *           x_j - mean                   CONSTANT
+ *           x_j                          NONE
+ *   pass 2  q = sum_{j < W} r_j * r_j;  c = sum_{j < W - Lg} r_j * r_{j + Lg}
+ *   var   = q / (W - 1)
+ *   ac    = c / q: the biased autocorrelation estimate (R's acf, statsmodels), not the Pearson
+ *           correlation of the shifted pair; NaN when q == 0
+ * Results, members contiguous in each:
+ *   out[4][nwin][nspec][n]   mean, slope, var, ac; an unused window stores NaN in all four.  Each
+ *                            out[i] is itself a series [nwin][nspec][n] that
+ *                            pm_series_group_stats and pm_series_kendall read as it stands
+ *   nused[nspec][n]          (int32) the number of used windows
+ * The result of a series depends on that member's values alone: not on the member's position in
+ * the batch, its neighbours, n or the launch geometry -- windows are independent, so a block may
+ * take any range of them.  pm_series_windows_geometry reports the tile of a (W, S): the adjacent
+ * members and the consecutive windows one block takes.
+ *
+ * pm_series_kendall -- per (index s, member m), over the pairs a < b of records of the window with
+ * x_a and x_b both finite:
+ *   conc[s][m]   the number of pairs with x_b > x_a
+ *   disc[s][m]   ... with x_b < x_a
+ *   tie[s][m]    ... with x_b == x_a
+ *   nfin[s][m]   the number of finite records
+ * (all int32; K <= PM_KENDALL_MAX = 4096, so K (K - 1) / 2 < 2^23).  Exact integers: no order and
+ * nothing to round.  tau-b against time, which has no ties, is the caller's to form:
+ * (conc - disc) / sqrt(n0 * (n0 - tie)), n0 = conc + disc + tie.
+ *
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): no NULL pointer where one is
+ * read or written; n, nspec, nrec >= 1; 0 <= k0 < k1 <= nrec; W, S, Lg in the ranges above;
+ * K >= W; a known detrend; stt equal to the entry's own value; nwin * nspec < 2^30;
+ * nspec <= 65535; (member tiles) * (window chunks) < 2^31; K <= PM_KENDALL_MAX for the trend.  */
+#define PM_WIN_MIN 4
+#define PM_WIN_MAX 4096
+#define PM_WIN_DETREND_NONE 0
+#define PM_WIN_DETREND_CONSTANT 1
+#define PM_WIN_DETREND_LINEAR 2
+#define PM_KENDALL_MAX 4096
+struct pm_series_windows {
+  int32_t n, nspec, nrec, k0, k1, window, step, lag, detrend, reserved;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  double stt;                            /* W (W^2 - 1) / 12                                      */
+};
+int pm_series_windows(const struct pm_series_windows *d, double *out, int32_t *nused,
+                      pm_stream_t stream);
+int pm_series_windows_geometry(int32_t window, int32_t step, int32_t *members, int32_t *windows);
+struct pm_series_kendall {
+  int32_t n, nspec, nrec, k0, k1, reserved1, reserved2, reserved3;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+};
+int pm_series_kendall(const struct pm_series_kendall *d, int32_t *conc, int32_t *disc,
+                      int32_t *tie, int32_t *nfin, pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ from .noise import NoiseForcing
 from .indices import RowIndices, IndexRecorder
 from .stats import SeriesStats
 from .spectra import SeriesSpectra
+from .windows import SeriesWindows
 from . import diagnostics
 from . import plotting
 from . import steady

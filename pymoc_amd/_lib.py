@@ -343,6 +343,24 @@ class pm_series_spectra(C.Structure):
               ("pair", C.c_void_p), ("pair_dev", c_dp), ("scale", C.c_double)]
 
 
+PM_WIN_MIN, PM_WIN_MAX, PM_KENDALL_MAX = 4, 4096, 4096
+PM_WIN_DETREND_NONE, PM_WIN_DETREND_CONSTANT, PM_WIN_DETREND_LINEAR = 0, 1, 2
+
+
+class pm_series_windows(C.Structure):
+  """Mirror of `struct pm_series_windows` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("window", C.c_int32), ("step", C.c_int32), ("lag", C.c_int32),
+              ("detrend", C.c_int32), ("reserved", C.c_int32), ("v", c_dp), ("stt", C.c_double)]
+
+
+class pm_series_kendall(C.Structure):
+  """Mirror of `struct pm_series_kendall` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("reserved1", C.c_int32), ("reserved2", C.c_int32),
+              ("reserved3", C.c_int32), ("v", c_dp)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -453,6 +471,11 @@ SIGNATURES = {
     "pm_series_member_stats": (C.c_int, [C.POINTER(pm_series_member_stats), c_dp, c_dp, c_dp, c_dp,
                                          C.c_void_p]),
     "pm_series_spectra": (C.c_int, [C.POINTER(pm_series_spectra), c_dp, c_dp, c_dp, c_dp,
+                                    C.c_void_p]),
+    "pm_series_windows": (C.c_int, [C.POINTER(pm_series_windows), c_dp, c_dp, C.c_void_p]),
+    "pm_series_windows_geometry": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]),
+    "pm_series_kendall": (C.c_int, [C.POINTER(pm_series_kendall), c_dp, c_dp, c_dp, c_dp,
                                     C.c_void_p]),
 }
 

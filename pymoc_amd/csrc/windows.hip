@@ -1,0 +1,361 @@
+// windows.hip -- sliding-window early-warning indicators of a recorded index series and the
+// Kendall trend of a series against its record number, computed where the series lives
+// (pymoc_amd.SeriesWindows).
+//
+// (no counterpart: what a user computes with a rolling apply over the downloaded series.)
+// Two entries over a series v[k][s][m] (record, index, member; an IndexRecorder's device layout)
+// and a record window [k0, k1).  include/pymoc_hip.h states the definitions: per sliding window the
+// two sequential passes (mean and slope, then the residual sums) with every product and sum
+// rounded on its own (-ffp-contract=off), and the pair counts of the trend.  Each double is
+// reproduced bit for bit by the NumPy restatement (tests/windows_cases.py); the counts are exact.
+//
+// K22 k_series_windows.  Windows are independent by definition, so a block takes a RANGE of them:
+// block x = (tile of TM adjacent members, chunk of NWB consecutive windows), block y = the index.
+// The block (1024 threads) stages the records its windows span -- W + (nw - 1) * S rows of TM
+// adjacent members, TM * 8 >= 32 contiguous bytes per row, 256 bytes up to W = 639 -- in LDS once:
+//   x[r][mi]     r < span, mi < TM
+// and a thread owns one (member, window) at a time: lane = mi + TM * slot, 1024 / TM windows in
+// flight, slot + p * (1024 / TM) in pass p.  It walks its window's W rows twice in ascending j,
+// the sums in registers; both walks read LDS only, members fastest over the lanes, so a 32-lane
+// half reads 32 / TM rows of TM consecutive doubles.  A byte of the series is fetched from global
+// memory span / (nw * S) times (wn_geometry: at most 6 where every thread can be kept busy, 5 at
+// W = 256, S = 1), and read from LDS about 3 W / S times.  nused is summed in LDS per block and
+// added to the zeroed output with one integer atomic per (member, block): integers, so no order
+// to speak of.
+//
+// K23 k_series_kendall.  block x = a tile of TM adjacent members, block y = the index.  The K
+// records of the tile are staged in LDS, a non-finite value as NaN -- every comparison with a NaN
+// is false, so such a pair counts nowhere without a branch.  A thread owns (member, a = slot,
+// slot + 1024 / TM, ..) and walks b = a + 1 .. K - 1 counting the concordant and the tied pairs in
+// int32 registers (K (K - 1) / 2 < 2^23); the counts are summed over the slots in LDS, and the
+// discordant pairs are the finite pairs, nfin (nfin - 1) / 2, less those two.
+#include <cmath>
+#include "common.hip.h"
+#include "launch.hip.h"
+
+namespace pm {
+
+constexpr int WN_THREADS = 1024;
+
+__device__ __forceinline__ bool wn_finite(double x) {
+  return fabs(x) <= 1.7976931348623157e308;  // false for NaN and +-inf
+}
+
+// The tile of a launch: TM adjacent members (32, 16, 8 or 4) and at most R records of LDS -- half
+// a CU's LDS (two blocks to a CU) or all of it.  nwb = the windows a block takes: what fits R, a
+// multiple of the WN_THREADS / TM windows in flight where it exceeds them.  Of the candidates,
+// widest rows first and the half before the whole, the first is taken that holds W records, keeps
+// every thread busy (nwb >= the windows in flight) and fetches a byte of the series at most six
+// times (span / (nwb * S)); failing that, the widest rows that hold W records in a whole CU's LDS.
+struct WnGeom {
+  int tm, ltm, R, nwb;
+};
+inline WnGeom wn_candidate(int W, int S, int ltm, size_t bytes) {
+  WnGeom g;
+  g.ltm = ltm;
+  g.tm = 1 << ltm;
+  g.R = (int)((bytes - sizeof(int) * g.tm) / (sizeof(double) * g.tm));  // (room for the counts)
+  g.nwb = 0;
+  if (g.R < W) return g;
+  const int slots = WN_THREADS / g.tm;
+  int nwb = (g.R - W) / S + 1;
+  if (nwb > slots) nwb -= nwb % slots;
+  g.nwb = nwb;
+  return g;
+}
+inline WnGeom wn_geometry(int W, int S) {
+  for (int ltm = 5; ltm >= 2; --ltm)
+    for (size_t bytes : {LDS_PER_CU / 2, LDS_PER_CU}) {
+      const WnGeom g = wn_candidate(W, S, ltm, bytes);
+      const long long span = W + (long long)(g.nwb - 1) * S;
+      if (g.nwb >= WN_THREADS / g.tm && span <= 6ll * g.nwb * S) return g;
+    }
+  for (int ltm = 5; ltm > 2; --ltm) {
+    const WnGeom g = wn_candidate(W, S, ltm, LDS_PER_CU);
+    if (g.nwb) return g;
+  }
+  return wn_candidate(W, S, 2, LDS_PER_CU);  // W <= 4096 < 5119: it fits
+}
+inline size_t wn_lds(const WnGeom &g, int span) {
+  return sizeof(double) * (size_t)span * g.tm + sizeof(int) * g.tm;
+}
+
+// The residual of the definition.
+template <int DET>
+__device__ __forceinline__ double wn_resid(double x, double mean, double slope, double t) {
+  if (DET == PM_WIN_DETREND_LINEAR) return (x - mean) - slope * t;
+  if (DET == PM_WIN_DETREND_CONSTANT) return x - mean;
+  return x;
+}
+
+template <int DET, bool LAG1>
+__global__ __launch_bounds__(WN_THREADS) void k_series_windows(
+    const double *__restrict__ v, int n, int nspec, int k0, int W, int S, int Lg, int nwin,
+    int nwb, int nchunks, int ltm, double stt, double *__restrict__ out,
+    int32_t *__restrict__ nused) {
+  extern __shared__ double wn_lds_[];
+  const int TM = 1 << ltm;
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks;
+  const int s = blockIdx.y;
+  const int m0 = tile << ltm;
+  const int i0 = chunk * nwb;                             // the block's first window
+  const int nw = nwin - i0 < nwb ? nwin - i0 : nwb;       // and how many it takes (>= 1)
+  const int span = W + (nw - 1) * S;                      // records staged: all inside [k0, k1)
+  double *x = wn_lds_;
+  int *cnt = (int *)(x + ((size_t)span << ltm));
+  const size_t rs = (size_t)nspec * (size_t)n;            // doubles between records
+  const int mi = tid & (TM - 1), slot = tid >> ltm, slots = WN_THREADS >> ltm;
+
+  // rows of TM adjacent members.  A member past the end reads the last one's values: they are in
+  // bounds, and nothing of it is stored.
+  {
+    const int mc = m0 + mi < n ? m0 + mi : n - 1;
+    const double *base = v + (size_t)(k0 + i0 * S) * rs + (size_t)s * n + mc;
+#pragma unroll 4
+    for (int r = slot; r < span; r += slots) x[(r << ltm) + mi] = base[(size_t)r * rs];
+  }
+  if (tid < TM) cnt[tid] = 0;
+  __syncthreads();
+
+  const double nan = __builtin_nan("");
+  const double half = 0.5 * (double)(W - 1);
+  const bool live = m0 + mi < n;
+  int used = 0;
+  for (int wl = slot; wl < nw; wl += slots) {
+    const double *xw = x + (((size_t)wl * S) << ltm) + mi;
+    // pass 1: the sums of x_j and of t_j * x_j
+    // (t_j = (double)j - half is formed by adding 1.0: multiples of a half below 2^12, so exact)
+    double sum = 0.0, st = 0.0, t = 0.0 - half;
+    bool fin = true;
+#pragma unroll 4
+    for (int j = 0; j < W; ++j) {
+      const double xj = xw[j << ltm];
+      fin = fin && wn_finite(xj);
+      sum = sum + xj;
+      if (DET == PM_WIN_DETREND_LINEAR) {
+        st = st + t * xj;
+        t = t + 1.0;
+      }
+    }
+    double mean = nan, slope = nan, var = nan, ac = nan;
+    if (fin) {
+      mean = sum / (double)W;
+      slope = DET == PM_WIN_DETREND_LINEAR ? st / stt : 0.0;
+      // pass 2: q = sum r_j r_j, c = sum_{j < W - Lg} r_j r_{j + Lg}
+      double q = 0.0, c = 0.0;
+      t = 0.0 - half;
+      if (LAG1) {
+        double prev = wn_resid<DET>(xw[0], mean, slope, t);
+        q = q + prev * prev;
+#pragma unroll 4
+        for (int j = 1; j < W; ++j) {
+          t = t + 1.0;
+          const double r = wn_resid<DET>(xw[j << ltm], mean, slope, t);
+          c = c + prev * r;
+          q = q + r * r;
+          prev = r;
+        }
+      } else {
+        const int nl = W - Lg;
+        const double dl = (double)Lg;
+#pragma unroll 2
+        for (int j = 0; j < nl; ++j) {
+          const double r = wn_resid<DET>(xw[j << ltm], mean, slope, t);
+          const double r2 = wn_resid<DET>(xw[(j + Lg) << ltm], mean, slope, t + dl);
+          q = q + r * r;
+          c = c + r * r2;
+          t = t + 1.0;
+        }
+#pragma unroll 2
+        for (int j = nl; j < W; ++j) {
+          const double r = wn_resid<DET>(xw[j << ltm], mean, slope, t);
+          q = q + r * r;
+          t = t + 1.0;
+        }
+      }
+      var = q / (double)(W - 1);
+      ac = c / q;
+      ++used;
+    }
+    if (live) {
+      const size_t plane = (size_t)nwin * rs;
+      double *o = out + ((size_t)(i0 + wl) * nspec + s) * n + m0 + mi;
+      o[0] = mean;
+      o[plane] = slope;
+      o[2 * plane] = var;
+      o[3 * plane] = ac;
+    }
+  }
+  if (used) atomicAdd(&cnt[mi], used);
+  __syncthreads();
+  if (tid < TM && m0 + tid < n && cnt[tid]) atomicAdd(&nused[(size_t)s * n + m0 + tid], cnt[tid]);
+}
+
+template <int DET, bool LAG1>
+int wn_launch(const struct pm_series_windows &d, int nwin, hipStream_t st, double *out,
+              int32_t *nused) {
+  const WnGeom g = wn_geometry(d.window, d.step);
+  const int nchunks = (nwin + g.nwb - 1) / g.nwb;
+  const long long ntiles = ((long long)d.n + g.tm - 1) / g.tm;
+  PM_REQUIRE(ntiles * nchunks < (1ll << 31),
+             "member tiles * window chunks = %lld is not below 2^31", ntiles * nchunks);
+  const int nw = nwin < g.nwb ? nwin : g.nwb;
+  const size_t lds = wn_lds(g, d.window + (nw - 1) * d.step);
+  auto kernel = k_series_windows<DET, LAG1>;
+  if (lds > LDS_DYN_UNRAISED)
+    PM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds));
+  PM_HIP(hipMemsetAsync(nused, 0, sizeof(int32_t) * (size_t)d.nspec * (size_t)d.n, st));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(ntiles * nchunks), (unsigned)d.nspec),
+                     dim3(WN_THREADS), lds, st, d.v, (int)d.n, (int)d.nspec, (int)d.k0,
+                     (int)d.window, (int)d.step, (int)d.lag, nwin, g.nwb, nchunks, g.ltm, d.stt,
+                     out, nused);
+  PM_HIP(hipGetLastError());
+  return PM_OK;
+}
+
+// ------------------------------------------------------------------ K23
+// TM members by K records of LDS: at most 64 KiB up to K = 2048, 128 KiB above.
+inline int kd_ltm(int K) { return K <= 256 ? 5 : K <= 512 ? 4 : K <= 1024 ? 3 : 2; }
+
+__global__ __launch_bounds__(WN_THREADS) void k_series_kendall(
+    const double *__restrict__ v, int n, int nspec, int k0, int K, int ltm,
+    int32_t *__restrict__ conc_out, int32_t *__restrict__ disc_out, int32_t *__restrict__ tie_out,
+    int32_t *__restrict__ nfin_out) {
+  extern __shared__ double wn_lds_[];
+  const int TM = 1 << ltm;
+  const int tid = threadIdx.x;
+  const int s = blockIdx.y, m0 = blockIdx.x << ltm;
+  double *x = wn_lds_;
+  int *cnt = (int *)(x + ((size_t)K << ltm));  // [3][TM]: conc, tie, nfin
+  const size_t rs = (size_t)nspec * (size_t)n;
+  const int mi = tid & (TM - 1), slot = tid >> ltm, slots = WN_THREADS >> ltm;
+  const double nan = __builtin_nan("");
+  if (tid < 3 * TM) cnt[tid] = 0;
+  int nfin = 0;
+  {
+    const int mc = m0 + mi < n ? m0 + mi : n - 1;
+    const double *base = v + (size_t)k0 * rs + (size_t)s * n + mc;
+#pragma unroll 4
+    for (int r = slot; r < K; r += slots) {
+      const double xr = base[(size_t)r * rs];
+      const bool fin = wn_finite(xr);
+      nfin += fin ? 1 : 0;
+      x[(r << ltm) + mi] = fin ? xr : nan;
+    }
+  }
+  __syncthreads();
+  // two of the three counts: a pair of finite values that is neither concordant nor tied is
+  // discordant, and the finite pairs are nfin (nfin - 1) / 2 -- integers, so exact
+  int conc = 0, tie = 0;
+  for (int a = slot; a < K - 1; a += slots) {
+    const double xa = x[(a << ltm) + mi];
+#pragma unroll 4
+    for (int b = a + 1; b < K; ++b) {
+      const double xb = x[(b << ltm) + mi];
+      conc += xb > xa ? 1 : 0;
+      tie += xb == xa ? 1 : 0;
+    }
+  }
+  atomicAdd(&cnt[mi], conc);
+  atomicAdd(&cnt[TM + mi], tie);
+  atomicAdd(&cnt[2 * TM + mi], nfin);
+  __syncthreads();
+  if (tid < TM && m0 + tid < n) {
+    const size_t o = (size_t)s * n + m0 + tid;
+    const int nf = cnt[2 * TM + tid], c = cnt[tid], t = cnt[TM + tid];
+    conc_out[o] = c;
+    disc_out[o] = nf * (nf - 1) / 2 - c - t;
+    tie_out[o] = t;
+    nfin_out[o] = nf;
+  }
+}
+
+}  // namespace pm
+
+using namespace pm;
+
+extern "C" {
+
+int pm_series_windows_geometry(int32_t window, int32_t step, int32_t *members, int32_t *windows) {
+  PM_REQUIRE(members && windows, "members or windows is NULL");
+  PM_REQUIRE(window >= PM_WIN_MIN && window <= PM_WIN_MAX, "window %d outside [%d, %d]", window,
+             PM_WIN_MIN, PM_WIN_MAX);
+  PM_REQUIRE(step >= 1 && step <= window, "step %d outside [1, window = %d]", step, window);
+  const WnGeom g = wn_geometry(window, step);
+  *members = g.tm;
+  *windows = g.nwb;
+  return PM_OK;
+}
+
+int pm_series_windows(const struct pm_series_windows *dp, double *out, int32_t *nused,
+                      pm_stream_t stream) {
+  PM_REQUIRE(dp, "d is NULL");
+  const struct pm_series_windows &d = *dp;
+  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nrec >= 1, "n %d, nspec %d or nrec %d < 1", d.n,
+             d.nspec, d.nrec);
+  PM_REQUIRE(0 <= d.k0 && d.k0 < d.k1 && d.k1 <= d.nrec,
+             "window [%d, %d) is not inside the %d records", d.k0, d.k1, d.nrec);
+  const int W = d.window;
+  PM_REQUIRE(W >= PM_WIN_MIN && W <= PM_WIN_MAX, "window length %d outside [%d, %d]", W,
+             PM_WIN_MIN, PM_WIN_MAX);
+  PM_REQUIRE(d.step >= 1 && d.step <= W, "step %d outside [1, window = %d]", d.step, W);
+  PM_REQUIRE(d.lag >= 1 && d.lag <= W - 2, "lag %d outside [1, window - 2 = %d]", d.lag, W - 2);
+  PM_REQUIRE(d.k1 - d.k0 >= W, "the record window [%d, %d) is shorter than the window length %d",
+             d.k0, d.k1, W);
+  PM_REQUIRE(d.detrend == PM_WIN_DETREND_NONE || d.detrend == PM_WIN_DETREND_CONSTANT ||
+                 d.detrend == PM_WIN_DETREND_LINEAR,
+             "unknown detrend %d", d.detrend);
+  const double stt = (double)W * ((double)W * (double)W - 1.0) / 12.0;  // an integer: exact
+  PM_REQUIRE(d.stt == stt, "stt %.17g is not W (W^2 - 1) / 12 = %.17g", d.stt, stt);
+  const int nwin = (d.k1 - d.k0 - W) / d.step + 1;
+  PM_REQUIRE((long long)nwin * d.nspec < (1ll << 30), "nwin * nspec = %lld is not below 2^30",
+             (long long)nwin * d.nspec);
+  PM_REQUIRE(d.nspec <= 65535, "nspec = %d > 65535", d.nspec);
+  PM_REQUIRE(d.v, "v is NULL");
+  PM_REQUIRE(out && nused, "out or nused is NULL");
+  hipStream_t st = resolve_stream(stream);
+  const bool lag1 = d.lag == 1;
+  switch (d.detrend) {
+    case PM_WIN_DETREND_LINEAR:
+      return lag1 ? wn_launch<PM_WIN_DETREND_LINEAR, true>(d, nwin, st, out, nused)
+                  : wn_launch<PM_WIN_DETREND_LINEAR, false>(d, nwin, st, out, nused);
+    case PM_WIN_DETREND_CONSTANT:
+      return lag1 ? wn_launch<PM_WIN_DETREND_CONSTANT, true>(d, nwin, st, out, nused)
+                  : wn_launch<PM_WIN_DETREND_CONSTANT, false>(d, nwin, st, out, nused);
+    default:
+      return lag1 ? wn_launch<PM_WIN_DETREND_NONE, true>(d, nwin, st, out, nused)
+                  : wn_launch<PM_WIN_DETREND_NONE, false>(d, nwin, st, out, nused);
+  }
+}
+
+int pm_series_kendall(const struct pm_series_kendall *dp, int32_t *conc, int32_t *disc,
+                      int32_t *tie, int32_t *nfin, pm_stream_t stream) {
+  PM_REQUIRE(dp, "d is NULL");
+  const struct pm_series_kendall &d = *dp;
+  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nrec >= 1, "n %d, nspec %d or nrec %d < 1", d.n,
+             d.nspec, d.nrec);
+  PM_REQUIRE(0 <= d.k0 && d.k0 < d.k1 && d.k1 <= d.nrec,
+             "window [%d, %d) is not inside the %d records", d.k0, d.k1, d.nrec);
+  const int K = d.k1 - d.k0;
+  PM_REQUIRE(K <= PM_KENDALL_MAX, "the window [%d, %d) holds %d records, more than %d", d.k0, d.k1,
+             K, PM_KENDALL_MAX);
+  PM_REQUIRE(d.nspec <= 65535, "nspec = %d > 65535", d.nspec);
+  PM_REQUIRE(d.v, "v is NULL");
+  PM_REQUIRE(conc && disc && tie && nfin, "conc, disc, tie or nfin is NULL");
+  hipStream_t st = resolve_stream(stream);
+  const int ltm = kd_ltm(K), tm = 1 << ltm;
+  const size_t lds = sizeof(double) * (size_t)K * tm + sizeof(int) * 3 * tm;
+  if (lds > LDS_DYN_UNRAISED)
+    PM_HIP(hipFuncSetAttribute((const void *)k_series_kendall,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_series_kendall, dim3((unsigned)(((long long)d.n + tm - 1) / tm),
+                                            (unsigned)d.nspec),
+                     dim3(WN_THREADS), lds, st, d.v, (int)d.n, (int)d.nspec, (int)d.k0, K, ltm,
+                     conc, disc, tie, nfin);
+  PM_HIP(hipGetLastError());
+  return PM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,284 @@
+"""SeriesWindows: sliding-window early-warning indicators of a recorded index series, on the device.
+
+A ramped noise ensemble is run to see whether the fluctuations of an index slow down and grow as
+a transition comes near: critical slowing down, read from the lag-1 autocorrelation and the
+variance of the detrended index in a sliding window, each followed through time and summarised by
+Kendall's tau of the indicator against time.  `SeriesWindows` computes, for every (index, member)
+series an `IndexRecorder` keeps on the device ([n_samples][nspec][n]), the mean, the linear slope,
+the variance and the lagged autocorrelation of every sliding window in ONE launch where the series
+lives (pm_series_windows, csrc/windows.hip), and the Kendall counts of a series against its record
+number in one more (pm_series_kendall); only the results are downloaded.
+
+  compute(k0, k1)          mean, slope, var, ac [name] -> [n, nwin] and nused[name] -> [n]
+  across_members(which)    the launch, then the indicator as a device series [nwin][nspec][n]
+                           through SeriesStats.across_members: the group mean and the quantile
+                           bands per window, no per-member indicator downloaded
+  trend(k0, k1)            the launch, then pm_series_kendall over the var and the ac series on the
+                           device: tau, conc, disc, tie, nfin [name] -> [n]; only the counts are
+                           downloaded
+  kendall(source, k0, k1)  the same counts and tau of any device series
+
+A window with a non-finite value is excluded and counted (`nused`), never propagated: its four
+indicators are NaN, which `across_members` and `trend` exclude and count in turn.  The definition
+is per window, two sequential passes with the op order include/pymoc_hip.h states, so every double
+equals the NumPy restatement (tests/windows_cases.py) bit for bit; the Kendall counts are exact
+integers.  `ac` is the biased autocorrelation estimate (R's acf, statsmodels), not the Pearson
+correlation of the shifted pair (pandas.Series.autocorr).  An indicator is dated at the END of its
+window (`record_end`), the early-warning convention.
+
+Out of scope:
+  * Gaussian-kernel detrending;
+  * skewness and higher moments;
+  * surrogate significance tests of tau;
+  * anything across ranks: every rank treats its own members;
+  * anything online: the indicators are computed from the recorded series, after the samples;
+  * indicators of `pos` (the positions an IndexRecorder keeps next to the values);
+  * linear detrending inside `SeriesSpectra`, which stays as it is.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, lib
+from .device import DeviceArray, _sh, launch_span
+from .stats import SeriesStats
+
+_DETREND = dict(linear=_lib.PM_WIN_DETREND_LINEAR, constant=_lib.PM_WIN_DETREND_CONSTANT,
+                none=_lib.PM_WIN_DETREND_NONE)
+INDICATORS = ("mean", "slope", "var", "ac")
+
+
+def stt_of(W):
+  """sum t_j^2 = W (W^2 - 1) / 12 of t_j = j - (W - 1) / 2: an integer below 2^53, exact."""
+  W = int(W)
+  return float(W * (W * W - 1) // 12)
+
+
+def tau_b(conc, disc, tie):
+  """Kendall's tau-b against time, which has no ties, from the pair counts: (conc - disc) /
+  sqrt(n0 * (n0 - tie)), n0 = conc + disc + tie; NaN for n0 == tie (no pair, or all equal)."""
+  conc, disc, tie = (np.asarray(a, dtype=np.float64) for a in (conc, disc, tie))
+  n0 = conc + disc + tie
+  with np.errstate(all="ignore"):
+    return (conc - disc) / np.sqrt(n0 * (n0 - tie))
+
+
+def _source(source, stream):
+  """(recorder or None, array, names, stream, (nrec, nspec, n)) of a source, checked as SeriesStats
+  checks it."""
+  rec = None
+  if isinstance(source, tuple):
+    if len(source) != 2:
+      raise ValueError("a source is an IndexRecorder or (DeviceArray [nrec, nspec, n], names)")
+    arr, names = source
+  else:
+    rec = source
+    arr, names, stream = source._values, source.table.names, source.ens.stream
+  shape = tuple(getattr(arr, "shape", ()))
+  if len(shape) != 3 or min(shape) < 1 or np.dtype(getattr(arr, "dtype", None)) != np.float64:
+    raise ValueError("the series must be a float64 device array [nrec, nspec, n] (shape %r here)"
+                     % (shape,))
+  names = list(names)
+  if len(names) != shape[1] or len(set(names)) != shape[1]:
+    raise ValueError("the series has %d indices but %d distinct names are given"
+                     % (shape[1], len(set(names))))
+  if shape[1] > 65535:
+    raise ValueError("nspec = %d is above 65535" % shape[1])
+  return rec, arr, names, stream, shape
+
+
+def _record_window(rec, nrec, k0, k1):
+  k0 = int(k0)
+  k1 = nrec if k1 is None else int(k1)
+  if not 0 <= k0 < k1 <= nrec:
+    raise ValueError("window [%d, %d) is not inside the %d records" % (k0, k1, nrec))
+  if rec is not None:
+    missing = np.nonzero(rec.steps[k0:k1] < 0)[0]
+    if missing.size:
+      raise ValueError("window [%d, %d) holds record %d, which was never written"
+                       % (k0, k1, k0 + missing[0]))
+  return k0, k1
+
+
+def _launch_kendall(arr, shape, k0, k1, stream, timer, out=None):
+  """pm_series_kendall over the records [k0, k1) of a device series: the four int32 [nspec, n]
+  count arrays on the device, nothing synchronised.  `out`: the arrays of an earlier call, written
+  again."""
+  nrec, nspec, n = shape
+  d = _lib.pm_series_kendall()
+  d.n, d.nspec, d.nrec, d.k0, d.k1, d.v = n, nspec, nrec, k0, k1, arr.ptr
+  if out is None:
+    out = [DeviceArray((nspec, n), np.int32) for _ in range(4)]
+  with launch_span(timer, "k_series_kendall", stream):
+    check(lib.pm_series_kendall(C.byref(d), out[0].ptr, out[1].ptr, out[2].ptr, out[3].ptr,
+                                _sh(stream)))
+  return out
+
+
+class Trend(object):
+  """Kendall's tau of a series against its record number and the counts it is formed from: tau,
+  conc, disc, tie, nfin, each `[name] -> [n]`."""
+
+  def __init__(self, names, conc, disc, tie, nfin):
+    self.names = list(names)
+    self.conc, self.disc, self.tie, self.nfin = ({nm: a[s] for s, nm in enumerate(self.names)}
+                                                 for a in (conc, disc, tie, nfin))
+    self.tau = {nm: tau_b(self.conc[nm], self.disc[nm], self.tie[nm]) for nm in self.names}
+
+
+def kendall(source, k0=0, k1=None, stream=None):
+  """The `Trend` of any device series over the records [k0, k1) (at most 4096 of them): one launch
+  of pm_series_kendall and the download of the counts.  `source` as for `SeriesWindows`."""
+  rec, arr, names, stream, shape = _source(source, stream)
+  k0, k1 = _record_window(rec, shape[0], k0, k1)
+  if k1 - k0 > _lib.PM_KENDALL_MAX:
+    raise ValueError("window [%d, %d) holds %d records, more than %d"
+                     % (k0, k1, k1 - k0, _lib.PM_KENDALL_MAX))
+  timer = rec.ens.timer if rec is not None else None
+  out = _launch_kendall(arr, shape, k0, k1, stream, timer)
+  return Trend(names, *(a.download(stream=stream) for a in out))
+
+
+class Windows(object):
+  """What `compute` returns: mean, slope, var, ac `[name] -> [n, nwin]`, nused `[name] -> [n]` and
+  record_end [nwin]."""
+
+  def __init__(self, names, record_end, out, nused):
+    # out [4, nwin, nspec, n]
+    self.names, self.record_end = list(names), record_end
+    for i, key in enumerate(INDICATORS):
+      setattr(self, key, {nm: np.ascontiguousarray(out[i, :, s, :].T)
+                          for s, nm in enumerate(self.names)})
+    self.nused = {nm: nused[s] for s, nm in enumerate(self.names)}
+
+
+class WindowTrend(object):
+  """What `trend` returns: `.var` and `.ac`, a `Trend` each."""
+
+  def __init__(self, var, ac):
+    self.var, self.ac = var, ac
+
+
+class SeriesWindows(object):
+  """`SeriesWindows(source, window, step=1, detrend="linear", lag=1, groups=None, stream=None)`.
+
+  source    an `IndexRecorder`, or `(DeviceArray [nrec, nspec, n], names)` for any device series
+            (`stream=` is then the stream the series is written on)
+  window    W, the records of a window, in [4, 4096]; any integer
+  step      S, the records between the starts of two consecutive windows, in [1, W]
+  detrend   "linear" (the window's least-squares line is removed), "constant" (its mean) or "none"
+  lag       Lg of the autocorrelation, in [1, W - 2]
+  groups    int array [n] of labels, for `across_members` (as SeriesStats)
+
+  Each call of `compute` / `across_members` / `trend` is one launch of pm_series_windows on the
+  source's stream (and what follows it on the device).  With a recorder as source a record window
+  that holds a record never written is a ValueError."""
+
+  def __init__(self, source, window, step=1, detrend="linear", lag=1, groups=None, stream=None):
+    self._rec, arr, self.names, self.stream, shape = _source(source, stream)
+    self.nrec, self.nspec, self.n = shape
+    for what, val in (("window", window), ("step", step), ("lag", lag)):
+      if not isinstance(val, (int, np.integer)) or isinstance(val, bool):
+        raise ValueError("%s must be an integer (%r here)" % (what, val))
+    W, S, Lg = int(window), int(step), int(lag)
+    if not _lib.PM_WIN_MIN <= W <= _lib.PM_WIN_MAX:
+      raise ValueError("window must lie in [%d, %d] (%d here)"
+                       % (_lib.PM_WIN_MIN, _lib.PM_WIN_MAX, W))
+    if not 1 <= S <= W:
+      raise ValueError("step must lie in [1, window = %d] (%d here)" % (W, S))
+    if not 1 <= Lg <= W - 2:
+      raise ValueError("lag must lie in [1, window - 2 = %d] (%d here)" % (W - 2, Lg))
+    if detrend not in _DETREND:
+      raise ValueError("unknown detrend %r (one of linear, constant, none)" % (detrend,))
+    self.window, self.step, self.lag, self.detrend = W, S, Lg, detrend
+    self.stt = stt_of(W)
+    self.groups = groups
+    if groups is not None:  # checked now, used by across_members
+      SeriesStats((arr, self.names), groups=groups)
+    self._series = arr
+
+  def _window(self, k0, k1):
+    k0, k1 = _record_window(self._rec, self.nrec, k0, k1)
+    if k1 - k0 < self.window:
+      raise ValueError("window [%d, %d) holds %d records, fewer than the window length %d"
+                       % (k0, k1, k1 - k0, self.window))
+    nwin = (k1 - k0 - self.window) // self.step + 1
+    if nwin * self.nspec >= 1 << 30:
+      raise ValueError("nwin * nspec = %d is not below 2^30" % (nwin * self.nspec))
+    return k0, k1, nwin
+
+  def nwin(self, k0=0, k1=None):
+    """The number of whole windows the record window [k0, k1) holds."""
+    return self._window(k0, k1)[2]
+
+  def record_end(self, k0=0, k1=None):
+    """The absolute record number of every window's last record [nwin]."""
+    k0, k1, nwin = self._window(k0, k1)
+    return k0 + np.arange(nwin) * self.step + self.window - 1
+
+  def _timer(self):
+    return self._rec.ens.timer if self._rec is not None else None
+
+  def _launch(self, k0, k1, nwin, out=None):
+    """The launch alone: (out [4, nwin, nspec, n], nused [nspec, n]) on the device, nothing
+    synchronised.  `out`: the arrays of an earlier call, written again."""
+    d = _lib.pm_series_windows()
+    d.n, d.nspec, d.nrec, d.k0, d.k1 = self.n, self.nspec, self.nrec, k0, k1
+    d.window, d.step, d.lag, d.detrend = self.window, self.step, self.lag, _DETREND[self.detrend]
+    d.v, d.stt = self._series.ptr, self.stt
+    if out is None:
+      out = (DeviceArray((4, nwin, self.nspec, self.n), np.float64),
+             DeviceArray((self.nspec, self.n), np.int32))
+    with launch_span(self._timer(), "k_series_windows", self.stream):
+      check(lib.pm_series_windows(C.byref(d), out[0].ptr, out[1].ptr, _sh(self.stream)))
+    return out
+
+  def compute(self, k0=0, k1=None):
+    k0, k1, nwin = self._window(k0, k1)
+    out, nused = self._launch(k0, k1, nwin)
+    return Windows(self.names, k0 + np.arange(nwin) * self.step + self.window - 1,
+                   out.download(stream=self.stream), nused.download(stream=self.stream))
+
+  def across_members(self, which, k0=0, k1=None, quantiles=()):
+    """The statistics, across the members of every group, of the indicator `which` ("mean",
+    "slope", "var" or "ac") as a series with the window for its record: a `stats.GroupStats` whose
+    arrays are [ngroups, nwin] (quantile: [nq, ngroups, nwin]).  A member's unused window is NaN:
+    SeriesStats excludes and counts it."""
+    if which not in INDICATORS:
+      raise ValueError("unknown indicator %r (one of %s)" % (which, ", ".join(INDICATORS)))
+    k0, k1, nwin = self._window(k0, k1)
+    out = (DeviceArray((4, nwin, self.nspec, self.n), np.float64),
+           DeviceArray((self.nspec, self.n), np.int32))
+    # (its argument checks come before the launch)
+    view = _Plane(out[0], INDICATORS.index(which), (nwin, self.nspec, self.n))
+    st = SeriesStats((view, self.names), groups=self.groups, quantiles=quantiles,
+                     stream=self.stream)
+    self.group_labels = st.group_labels
+    self._launch(k0, k1, nwin, out=out)
+    return st.across_members()
+
+  def trend(self, k0=0, k1=None):
+    """Kendall's tau against time of the var and of the ac series of every (index, member): the
+    launch, then pm_series_kendall over out[2] and out[3] on the device.  NaN windows (unused, or
+    ac of a window without variance) are left out of the pairs and show in nfin."""
+    k0, k1, nwin = self._window(k0, k1)
+    if nwin > _lib.PM_KENDALL_MAX:
+      raise ValueError("the record window [%d, %d) holds %d windows, more than %d"
+                       % (k0, k1, nwin, _lib.PM_KENDALL_MAX))
+    out, _ = self._launch(k0, k1, nwin)
+    shape = (nwin, self.nspec, self.n)
+    res = []
+    for i in (2, 3):
+      cnt = _launch_kendall(_Plane(out, i, shape), shape, 0, nwin, self.stream, self._timer())
+      res.append(Trend(self.names, *(a.download(stream=self.stream) for a in cnt)))
+    return WindowTrend(*res)
+
+
+class _Plane(object):
+  """out[i] of a device array out[4][nwin][nspec][n] as a device series of its own: an address, a
+  shape and a dtype (the parent owns the memory and is kept alive)."""
+
+  def __init__(self, parent, i, shape):
+    self._parent, self.shape, self.dtype = parent, tuple(shape), np.dtype(np.float64)
+    self.ptr = parent.ptr + 8 * i * int(np.prod(shape))
