@@ -649,6 +649,51 @@ __device__ __forceinline__ unsigned conv_variant(const ConvCache<P> &cc) {
   }
 }
 
+// Time-loop class of the cached pattern: conv_variant's slot set, or CONV_SURF (P <= 2) for the
+// SURFACE-ONLY pattern -- level nz - 1 alone convects, its adjusted value exceeds bs, and the lane
+// holds exactly that value.  Level nz - 1 is a boundary level of the step (it advances with dt = 0),
+// so it still holds the adjusted value at the next convect, `b > bs` is true again and the select
+// rewrites the same number: such a pattern verifies and rewrites a constant, and its loop tests
+// that lane once per block instead (conv_spec_run).  With N2min = 0 the adjusted value is bs
+// itself, the level stops convecting at the next step, and the column is not of this class.
+constexpr unsigned CONV_SURF = 4u;
+// the cached masks hold exactly one bit, that of level nz - 1 (scalar work only)
+template <int P>
+__device__ __forceinline__ bool conv_surface_only(const ConvCache<P> &cc, int nz) {
+  if constexpr (P <= 2) {
+    bool only = nz >= 2;
+    const int ls = (nz - 1) / P, ps = (nz - 1) % P;
+#pragma unroll
+    for (int p = 0; p < P; ++p) only = only && (cc.mask[p] == ((p == ps) ? (1ull << ls) : 0ull));
+    return only;
+  } else {
+    return false;
+  }
+}
+template <int P>
+__device__ __forceinline__ unsigned conv_class(const ConvCache<P> &cc, const double (&b)[P],
+                                               const double (&z)[P], double bs, double N2min,
+                                               int nz, long long &surf_bits) {
+  // surf_bits: the surface's adjusted value for CONV_SURF, as a wave-uniform bit pattern
+  const unsigned need = conv_variant<P>(cc);
+  surf_bits = 0;
+  if constexpr (P <= 2) {
+    if (conv_surface_only<P>(cc, nz)) {
+      // on the surface's z and b as wave-uniform values (v_readlane): this runs where the
+      // invariants of every time loop are live, and per-lane temporaries here set the kernel's
+      // register count
+      const double zs = level_value<P>(z, nz - 1), held = level_value<P>(b, nz - 1);
+      const double adj = bs + N2min * (zs - cc.zconv);  // column.py:268
+      const bool is = adj > bs && __double_as_longlong(held) == __double_as_longlong(adj);
+      if (__builtin_amdgcn_ballot_w64(is) != 0ull) {
+        surf_bits = __double_as_longlong(lane_value(adj, 0));
+        return CONV_SURF;
+      }
+    }
+  }
+  return need;
+}
+
 // Speculative convective time loop of a wave-owned column (G = 64), steps [s, nsteps).
 // Every step adjusts with the facts of the last ESTABLISHED convecting pattern cc (its zconv,
 // hence the adjusted values bs + N2min (z - zconv), column.py:268) and issues the step's
@@ -656,23 +701,60 @@ __device__ __forceinline__ unsigned conv_variant(const ConvCache<P> &cc) {
 // steps, and only a changed pattern (rare) redoes the block exactly from the saved b and
 // re-establishes cc.  Nothing leaves the registers before the check, so steps computed past
 // a pattern change are simply discarded.
-//   * SEL names the slots whose cached mask is non-zero.  Those slots compare (`b > bs`), select
-//     the adjusted value and fold `mask ^ cached` into a scalar accumulator (s_xor / s_or).
+//   * SEL names the slots in which the pattern's class (conv_class) has convecting lanes: the
+//     class itself or, for CONV_SURF (`surf`, a wave-uniform argument of the SEL = 0 loops: the
+//     two classes differ in the block check alone), none.  The SEL slots compare (`b > bs`),
+//     select the adjusted value and fold `mask ^ cached` into a scalar accumulator (s_xor / s_or).
 //   * In the other slots nothing convects under the cached pattern, so they need no select, and
 //     "still nothing convects" is one running v_max per step, compared with bs once per block
 //     (a NaN never convects in the reference -- `b > bs` is False -- and v_max ignores it).
+//   * CONV_SURF: the surface lane is left out of that test; the block check compares its 64-bit
+//     pattern with the adjusted value instead.  It holds that
+//     value, advances by b + 0 x, and so can only stay or turn NaN (x non-finite: a blown-up
+//     neighbour) and stay NaN; equal bits at the check mean the value convected, and was rewritten
+//     unchanged, at every step of the block.
+//   * IF != 0 (P <= 2, classes 0 and CONV_SURF): the running maxima of all slots are ONE integer
+//     maximum per step over the high dwords.  For a finite bs > 0, `b > bs` implies b > 0 and
+//     hence hi32(b) >= hi32(bs) as signed integers, so `acc >= hi32(bs)` can only raise false
+//     alarms (a level in bs's 2^-20 bucket, a positive NaN), never miss.  The surface lane and the
+//     padding lanes are excluded: in class 0 the surface holds bs itself (or NaN), which never
+//     convects.  The lane that holds the surface must hold no tested level, so the operands depend
+//     on the parity of nz at P = 2 --
+//       IF = 1 (P = 1, or nz odd): hi32(b[0]), hi32(b[1]): the surface's lane holds it and padding;
+//       IF = 2 (nz even):          hi32(b[0] of the next lane), hi32(b[1]): levels 2l+1 and 2l+2 in
+//         lane l, the surface with padding again.  The shifted value is the one the step fetches
+//         anyway; level 0 is then not tested: it holds bbot (or NaN), and the caller takes this
+//         loop only when bbot > bs is false.
+//     Any alarm, true or false, redoes the block exactly and clears `filt`: the caller finishes
+//     the launch in the v_max_f64 loop, so a persistent false alarm costs one block.
 // Why blocks: for a lone wave every scalar instruction costs a vector issue slot and a
 // conditional branch several; the 3-instruction loop control and the check's compare + branch
 // are paid once per UNR steps.  Returns the number of steps done when the new pattern belongs
-// to another SEL class (the caller re-dispatches) or at nsteps.
-template <int P, int DIV, unsigned SEL, bool UA = false>
+// to another class (the caller re-dispatches) or at nsteps.
+// CLS: the kernel has the two mechanisms at all (k_column_steps_cls, the twin that
+// launches of at least 64 steps run).  Without it this function is the loop as it was before them,
+// instruction for instruction.
+// What the caller's dispatch knows about the class (wave-uniform; unused without CLS).
+struct ConvCls {
+  int surf = 0;             // -1 for CONV_SURF (a mask, in a scalar register for certain), else 0
+  long long surf_bits = 0;  // CONV_SURF: the surface's adjusted value, from conv_class
+  bool filt = false;        // the integer filter is valid and has raised no alarm yet
+};
+template <int P, int DIV, unsigned SEL, int IF, bool UA = false, bool CLS = false>
 __device__ __forceinline__ int conv_spec_run(const ColGrid<P> &g, ColRegs<P> &r,
                                              const double (&wA)[P], double dt, double bs,
                                              double bbot, double N2min, int lane, int nz,
-                                             ConvCache<P> &cc, int s, int nsteps) {
+                                             ConvCache<P> &cc, ConvCls &cls, int s, int nsteps) {
+  static_assert(IF == 0 || (CLS && P <= 2 && SEL == 0u), "the integer filter serves slots outside SEL");
+  constexpr bool SURFCLS = CLS && SEL == 0u && P <= 2;  // these loops also serve CONV_SURF
+  static_assert(IF != 2 || P == 2, "the shifted operands pair two slots");
   constexpr int UNR = P <= 2 ? 16 : (P <= 4 ? 2 : 1);
   double adjv[P];    // column.py:268 for the cached zconv: changes only with the pattern
   double bs_eff[P];  // bs for real levels, +inf for padding: `b > bs_eff` is the whole test
+  // all ones for CONV_SURF: the block check's two surface terms are scalar mask arithmetic, opaque
+  // to the optimiser (as `if (surf)` they became branches inside the hot loops, and the kernel
+  // took 152 VGPRs instead of 96)
+  const unsigned long long surf_mask = (unsigned long long)(long long)cls.surf;
   // Level 0 always ends a step's convect + boundary condition holding bbot (column.py:232
   // overwrites whatever convect wrote), so its "adjusted" value is bbot itself.
   auto set_adj = [&]() {
@@ -682,19 +764,30 @@ __device__ __forceinline__ int conv_spec_run(const ColGrid<P> &g, ColRegs<P> &r,
   };
   set_adj();
 #pragma unroll
-  for (int p = 0; p < P; ++p) bs_eff[p] = (lane * P + p < nz) ? bs : __builtin_inf();
+  for (int p = 0; p < P; ++p)
+    bs_eff[p] = (lane * P + p < nz) ? bs : __builtin_inf();
   double b_blk[P];          // state at the start of the current block
   unsigned long long acc;   // OR of (mask ^ cached) over the SEL slots and steps of the block
-  double bmax[P];           // running max of b over the block, slots outside SEL
+  double bmax[P];           // running max of b over the block, slots outside SEL (IF == 0)
+  int imax;                 // running max of hi32(b) over the block (IF != 0)
   auto spec = [&]() {
     unsigned long long im[P];
     bool ind[P];
+    if constexpr (IF == 1) {
+      imax = imax > __double2hiint(r.b[0]) ? imax : __double2hiint(r.b[0]);
+      if constexpr (P == 2) imax = imax > __double2hiint(r.b[1]) ? imax : __double2hiint(r.b[1]);
+    } else if constexpr (IF == 2) {
+      // (the very call from_next_lane_z makes inside the step: one DPP move serves both)
+      const int nh = __builtin_amdgcn_update_dpp(0, __double2hiint(r.b[0]), 0x130, 0xf, 0xf, true);
+      imax = imax > nh ? imax : nh;
+      imax = imax > __double2hiint(r.b[1]) ? imax : __double2hiint(r.b[1]);
+    }
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       if (((SEL >> p) & 1u) != 0u) {  // folds after unrolling
         ind[p] = r.b[p] > bs_eff[p];  // column.py:264
         im[p] = __builtin_amdgcn_ballot_w64(ind[p]);
-      } else {
+      } else if constexpr (IF == 0) {
         bmax[p] = __builtin_fmax(bmax[p], r.b[p]);
       }
     }
@@ -722,6 +815,7 @@ __device__ __forceinline__ int conv_spec_run(const ColGrid<P> &g, ColRegs<P> &r,
   };
   auto block_begin = [&]() {
     acc = 0ull;
+    imax = -__INT_MAX__ - 1;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       b_blk[p] = r.b[p];
@@ -730,10 +824,36 @@ __device__ __forceinline__ int conv_spec_run(const ColGrid<P> &g, ColRegs<P> &r,
   };
   auto block_bad = [&]() -> bool {
     bool conv = false;  // a lane of a slot outside SEL would convect
+    if constexpr (IF != 0) {
+      // alarm at imax >= hi32(bs) in a tested lane: those below the surface's, as a scalar mask
+      // (per-lane thresholds, being loop invariants, would stay live across the caller's
+      // dispatch, in all its loops)
+      const int hb = __builtin_amdgcn_readfirstlane(__double2hiint(bs));
+      unsigned long long alarm = __builtin_amdgcn_ballot_w64(imax >= hb);
+      asm("" : "+s"(alarm));  // (opaque, as `any` below)
+      acc |= alarm & ((1ull << ((nz - 1) / P)) - 1ull);
+    } else if constexpr (SURFCLS) {
+      // One ballot per SLOT: for CONV_SURF the surface's verdict does not count, and only its own
+      // slot's -- at P = 2 and even nz the other slot of its lane holds level nz - 2, the first to
+      // join.  (Masked here, not through a bs_eff of its own, for the same reason as above.)
+      const unsigned long long surf_lane = (1ull << ((nz - 1) / P)) & surf_mask;
 #pragma unroll
-    for (int p = 0; p < P; ++p)
-      if (((SEL >> p) & 1u) == 0u) conv = conv || (bmax[p] > bs_eff[p]);
-    if constexpr (SEL != (1u << P) - 1u) {
+      for (int p = 0; p < P; ++p) {
+        unsigned long long any = __builtin_amdgcn_ballot_w64(bmax[p] > bs_eff[p]);
+        asm("" : "+s"(any));  // (opaque, as `any` below)
+        acc |= any & ~((p == (nz - 1) % P) ? surf_lane : 0ull);
+      }
+    } else {
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+        if (((SEL >> p) & 1u) == 0u) conv = conv || (bmax[p] > bs_eff[p]);
+    }
+    if constexpr (SURFCLS) {
+      // the surface no longer holds its adjusted value (bit pattern, so that a NaN counts);
+      // by v_readlane and scalar logic: as a per-lane test it cost the kernel 4 VGPRs
+      acc |= (unsigned long long)(__double_as_longlong(level_value<P>(r.b, nz - 1)) ^ cls.surf_bits) & surf_mask;
+    }
+    if constexpr (SEL != (1u << P) - 1u && !SURFCLS) {
       // opaque to the optimiser: it would turn `ballot(conv) != 0` back into a DIVERGENT
       // branch on conv, and the structuriser then wraps the whole loop in exec-mask logic
       unsigned long long any = __builtin_amdgcn_ballot_w64(conv);
@@ -754,7 +874,8 @@ __device__ __forceinline__ int conv_spec_run(const ColGrid<P> &g, ColRegs<P> &r,
   };
   // Blocks of UNR steps, then of 4, then of 1.  The only loop-carried scalar of a tier is the count of blocks left;
   // single-exit loops (a `return` inside makes the compiler wrap the hot path in flag logic): a
-  // pattern of another SEL class ends the loop through its own counter.
+  // pattern of another class (or any alarm of the integer filter) ends the loop through its own
+  // counter.
   int pos = s, ret = -1;
   auto tier = [&](auto U) {
     constexpr int N = decltype(U)::value;
@@ -766,7 +887,19 @@ __device__ __forceinline__ int conv_spec_run(const ColGrid<P> &g, ColRegs<P> &r,
       for (int k = 0; k < N; ++k) spec();
       if (__builtin_expect(block_bad(), 0)) {
         redo(N);
-        if (conv_variant<P>(cc) != SEL) {
+        bool leave;
+        if constexpr (IF != 0) {
+          cls.filt = false;
+          leave = true;
+        } else if constexpr (CLS) {
+          // (a surface-only pattern, before or after: the caller decides whether it is of class
+          // CONV_SURF -- the vector work of conv_class here, inside every loop, cost the kernel a
+          // wave per SIMD)
+          leave = cls.surf != 0 || conv_variant<P>(cc) != SEL || conv_surface_only<P>(cc, nz);
+        } else {
+          leave = conv_variant<P>(cc) != SEL;
+        }
+        if (leave) {
           ret = s_end - (left - 1) * N;
           left = 1;
         } else {
@@ -835,9 +968,15 @@ __device__ __forceinline__ void col_pin(double (&b)[P]) {
 // UA (launch-level: pm_columns.reserved & PM_COLS_ALL_UNIFORM_AREA): Area and its reciprocal pair
 // are three scalars instead of three P-element arrays -- 12 registers at P = 2, which is what
 // separates 4 from 5 waves per SIMD (108 -> 96).
-template <int G, int P, int FAST, bool PLAIN, bool UA = false>
-__global__ __launch_bounds__(256) void k_column_steps(
-    pm_columns c, const double *__restrict__ wA_g, const double *__restrict__ vdx_g,
+// CLS (k_column_steps_cls; G = 64, P <= 2, PLAIN, UA): the twin with the surface-only class and the integer filter of
+// the speculative convective loop (conv_class, conv_spec_run).  launch_column_kernel runs it for
+// launches of at least 64 steps -- those that run the 16-step blocks.  Shorter launches (the coupled
+// drivers' 24 steps: new forcing, often a new pattern, every launch) run the kernel without it,
+// whose code the twin leaves untouched: with both mechanisms in ONE kernel it was 48 % larger and
+// config 4's K1, at 8 waves per SIMD in as many different loops, 1 to 9 % slower.
+template <int G, int P, int FAST, bool PLAIN, bool UA, bool CLS>
+__device__ __forceinline__ void column_steps_body(
+    const pm_columns &c, const double *__restrict__ wA_g, const double *__restrict__ vdx_g,
     const double *__restrict__ bin_g, double dt, int nsteps, int ops) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int lg = threadIdx.x % G;
@@ -989,20 +1128,53 @@ __global__ __launch_bounds__(256) void k_column_steps(
         if (lg == 0) r.b[0] = bbot;
         col_vertadvdiff<G, P, DIV, false, false, UA>(g, r, wA, dt, true, bs, bbot, false, 0., lg, nz);
         int s = 1;
-        while (s < nsteps) {  // one pass per established pattern class (rarely more than one)
-          const unsigned v = conv_variant<P>(cc);
-          if constexpr (P <= 2) {
-            switch (v) {
-              case 0: s = conv_spec_run<P, DIV, 0u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
-              case 1: s = conv_spec_run<P, DIV, 1u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
-              case 2: s = conv_spec_run<P, DIV, 2u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
-              default: s = conv_spec_run<P, DIV, 3u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps); break;
+        if constexpr (!CLS) {
+          while (s < nsteps) {  // one pass per established pattern class (rarely more than one)
+            const unsigned v = conv_variant<P>(cc);
+            ConvCls cls;
+#define PM_SPEC(SEL) \
+  s = conv_spec_run<P, DIV, SEL, 0, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, cls, s, nsteps)
+            if constexpr (P <= 2) {
+              switch (v) {
+                case 0: PM_SPEC(0u); break;
+                case 1: PM_SPEC(1u); break;
+                case 2: PM_SPEC(2u); break;
+                default: PM_SPEC(3u); break;
+              }
+            } else {
+              if (v == 0u)
+                PM_SPEC(0u);
+              else
+                PM_SPEC((1u << P) - 1u);
             }
-          } else {
-            if (v == 0u)
-              s = conv_spec_run<P, DIV, 0u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps);
-            else
-              s = conv_spec_run<P, DIV, (1u << P) - 1u, UA>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, s, nsteps);
+#undef PM_SPEC
+          }
+        } else {
+          static_assert(!CLS || (G == 64 && P <= 2), "the class loops exist for P <= 2");
+          // The integer filter of classes 0 and CONV_SURF (conv_spec_run) is valid for a finite,
+          // normal bs > 0 and, because its shifted form does not test level 0, a bbot that does not
+          // exceed bs.  One alarm clears it for the rest of the launch.
+          ConvCls cls;
+          const unsigned hb = (unsigned)__builtin_amdgcn_readfirstlane(__double2hiint(bs));
+          cls.filt = hb - 0x00100000u < 0x7fe00000u && __builtin_amdgcn_ballot_w64(bbot > bs) == 0ull;
+          const bool shifted = P == 2 && (nz & 1) == 0;  // (which operands the filter takes)
+          while (s < nsteps) {  // one pass per established pattern class (rarely more than one)
+            const unsigned v = conv_class<P>(cc, r.b, g.z, bs, N2min, nz, cls.surf_bits);
+            // (CONV_SURF runs in the loops of class 0)
+            cls.surf = __builtin_amdgcn_readfirstlane(v == CONV_SURF ? -1 : 0);
+#define PM_SPEC(SEL, IF) \
+  s = conv_spec_run<P, DIV, SEL, IF, UA, true>(g, r, wA, dt, bs, bbot, N2min, lane, nz, cc, cls, s, nsteps)
+            switch (v) {
+              case 1: PM_SPEC(1u, 0); break;
+              case 2: PM_SPEC(P == 2 ? 2u : 1u, 0); break;
+              case 3: PM_SPEC(P == 2 ? 3u : 1u, 0); break;
+              default:  // 0, CONV_SURF
+                if (!cls.filt) PM_SPEC(0u, 0);
+                else if (shifted) PM_SPEC(0u, P == 2 ? 2 : 1);
+                else PM_SPEC(0u, 1);
+                break;
+            }
+#undef PM_SPEC
           }
         }
       } else {
@@ -1081,6 +1253,21 @@ __global__ __launch_bounds__(256) void k_column_steps(
   }
 
   col_store_result<G, P>(c, r, base, col, col_ok, lg, lane, nz);
+}
+
+// (the body is a function so that the two kernels keep their own names: k_column_steps is, name
+// and code, the kernel it was before the twin)
+template <int G, int P, int FAST, bool PLAIN, bool UA = false>
+__global__ __launch_bounds__(256) void k_column_steps(
+    pm_columns c, const double *__restrict__ wA_g, const double *__restrict__ vdx_g,
+    const double *__restrict__ bin_g, double dt, int nsteps, int ops) {
+  column_steps_body<G, P, FAST, PLAIN, UA, false>(c, wA_g, vdx_g, bin_g, dt, nsteps, ops);
+}
+template <int G, int P, int FAST, bool PLAIN, bool UA>
+__global__ __launch_bounds__(256) void k_column_steps_cls(
+    pm_columns c, const double *__restrict__ wA_g, const double *__restrict__ vdx_g,
+    const double *__restrict__ bin_g, double dt, int nsteps, int ops) {
+  column_steps_body<G, P, FAST, PLAIN, UA, true>(c, wA_g, vdx_g, bin_g, dt, nsteps, ops);
 }
 
 // ------------------------------------------------------------------ streaming kernel
@@ -1533,6 +1720,17 @@ int launch_column_kernel(const ColumnPlan &pl, const pm_columns &c, const double
                        (ops & PM_OP_WEFF) != 0);
   } else {
     // (PM_OP_CONTRACTED selected the instantiation; PM_OP_WA_TWOBASIN's third array is in vdx)
+    // (long launches of the one-wave-per-column UA rows: the CLS twin, see k_column_steps; the
+    // row and the name column_kernel_name reports stay those of the kernel without it)
+    constexpr bool twin = G == 64 && P <= 2 && k.plain && k.ua;
+    if constexpr (twin) {
+      if (nsteps >= 64) {
+        hipLaunchKernelGGL((k_column_steps_cls<G, P, k.fast, k.plain, k.ua>), dim3(pl.grid), dim3(256),
+                           0, st, c, wA, vdx, bin, dt, nsteps, ops & ~PM_OP_CONTRACTED);
+        PM_HIP(hipGetLastError());
+        return PM_OK;
+      }
+    }
     hipLaunchKernelGGL((k_column_steps<G, P, k.fast, k.plain, k.ua>), dim3(pl.grid), dim3(256), 0,
                        st, c, wA, vdx, bin, dt, nsteps, ops & ~PM_OP_CONTRACTED);
   }
