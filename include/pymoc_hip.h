@@ -287,6 +287,12 @@ int pm_column_kernel_shape(int32_t ncols, int32_t nz, int32_t lanes_per_col,
 int pm_column_kernel_name(const pm_columns *cols, const double *wA, const double *vdx_in,
                           int32_t nsteps, int32_t ops, int32_t lanes_per_col, char *name,
                           size_t name_len);
+/* *twin = 1 when pm_column_steps with these arguments runs k_column_steps_cls, the twin of the
+ * one-wave-per-column uniform-Area rows (G = 64, at most 2 levels per lane, plain timesteps) that
+ * launches of at least 64 steps take; 0 otherwise, and when the call launches nothing.
+ * pm_column_kernel_name reports the row's name either way.  The same checks, reporting only.  */
+int pm_column_kernel_twin(const pm_columns *cols, const double *wA, const double *vdx_in,
+                          int32_t nsteps, int32_t ops, int32_t lanes_per_col, int32_t *twin);
 
 /* ------------------------------------------------------------------ Psi_Thermwind
  * Replaces pymoc.modules.Psi_Thermwind for n independent members on one grid z[nz]:

@@ -415,6 +415,8 @@ SIGNATURES = {
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pm_column_kernel_name": (C.c_int, [C.POINTER(pm_columns), c_dp, c_dp, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_char_p, C.c_size_t]),
+    "pm_column_kernel_twin": (C.c_int, [C.POINTER(pm_columns), c_dp, c_dp, C.c_int32, C.c_int32,
+                                        C.c_int32, C.POINTER(C.c_int32)]),
     "pm_thermwind_update": (C.c_int, [C.POINTER(pm_thermwind), C.c_int32, C.c_void_p]),
     "pm_thermwind_residuals": (C.c_int, [C.c_int32] + [c_dp] * 6 + [C.c_void_p]),
     "pm_psi_so_update": (C.c_int, [C.POINTER(pm_psi_so), C.c_int32, C.c_void_p]),

@@ -364,6 +364,24 @@ class ColumnBatch(object):
                                     int(lanes_per_col), buf, 96))
     return buf.value.decode()
 
+  def kernel_twin(self, nsteps, lanes_per_col=0, ops=_lib.PM_OP_TIMESTEP, horadv=False,
+                  arith="exact", precombined=False, wA=None):
+    """True when `steps(...)` with these arguments runs `k_column_steps_cls`, the twin that
+    launches of at least 64 steps of the one-wave-per-column uniform-Area rows take
+    (`pm_column_kernel_twin`; `kernel_name` reports the row's name either way).  Arguments as
+    for `kernel_name`."""
+    if precombined:
+      ops = ops | _lib.PM_OP_WEFF
+    if arith == "contracted":
+      ops = ops | _lib.PM_OP_CONTRACTED
+    forcing = wA.ptr if isinstance(wA, DeviceArray) else _ALIGNED_ADDRESS
+    vdx = _ALIGNED_ADDRESS if horadv or ops & _lib.PM_OP_WA_TWOBASIN else None
+    d = self.descriptor()
+    twin = C.c_int32(0)
+    check(lib.pm_column_kernel_twin(C.byref(d), forcing, vdx, int(nsteps), int(ops),
+                                    int(lanes_per_col), C.byref(twin)))
+    return bool(twin.value)
+
   def combine_forcing(self, wA, out=None):
     """weff = wA - d(A kappa)/dz of each column's coefficient set in use, on the device
     (`pm_column_weff`), for `steps(weff, ..., precombined=True)`: wA is static between two

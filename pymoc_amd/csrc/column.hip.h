@@ -1704,6 +1704,18 @@ inline int column_kernel_name(const ColumnPlan &pl, char *name, size_t len) {
   return PM_OK;
 }
 
+// The CLS twin (k_column_steps_cls, see k_column_steps): which rows have one, and from how many
+// steps per launch it runs -- those that run the 16-step blocks.  launch_column_kernel and
+// pm_column_kernel_twin both ask here.
+constexpr int CLS_MIN_STEPS = 64;
+constexpr bool column_twin_row(const ColKernel &k, int G, int P) {
+  return !k.stream && G == 64 && P <= 2 && k.plain && k.ua;
+}
+inline bool column_runs_twin(const ColumnPlan &pl, int nsteps) {
+  return pl.kernel != CK_NONE && column_twin_row(col_kernel(pl.kernel), pl.G, pl.P) &&
+         nsteps >= CLS_MIN_STEPS;
+}
+
 template <int G, int P, ColKernelId K>
 int launch_column_kernel(const ColumnPlan &pl, const pm_columns &c, const double *wA,
                          const double *vdx, const double *bin, double dt, int nsteps, int ops,
@@ -1722,9 +1734,8 @@ int launch_column_kernel(const ColumnPlan &pl, const pm_columns &c, const double
     // (PM_OP_CONTRACTED selected the instantiation; PM_OP_WA_TWOBASIN's third array is in vdx)
     // (long launches of the one-wave-per-column UA rows: the CLS twin, see k_column_steps; the
     // row and the name column_kernel_name reports stay those of the kernel without it)
-    constexpr bool twin = G == 64 && P <= 2 && k.plain && k.ua;
-    if constexpr (twin) {
-      if (nsteps >= 64) {
+    if constexpr (column_twin_row(k, G, P)) {
+      if (nsteps >= CLS_MIN_STEPS) {
         hipLaunchKernelGGL((k_column_steps_cls<G, P, k.fast, k.plain, k.ua>), dim3(pl.grid), dim3(256),
                            0, st, c, wA, vdx, bin, dt, nsteps, ops & ~PM_OP_CONTRACTED);
         PM_HIP(hipGetLastError());

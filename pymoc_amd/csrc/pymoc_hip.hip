@@ -452,6 +452,16 @@ int pm_column_kernel_name(const pm_columns *cols, const double *wA, const double
   return column_kernel_name(pl, name, name_len);
 }
 
+int pm_column_kernel_twin(const pm_columns *cols, const double *wA, const double *vdx_in,
+                          int32_t nsteps, int32_t ops, int32_t lanes_per_col, int32_t *twin) {
+  PM_REQUIRE(twin, "NULL output");
+  ColumnPlan pl;
+  const int rc = column_call(cols, wA, vdx_in, nsteps, ops, lanes_per_col, &pl);
+  if (rc != PM_OK) return rc;
+  *twin = column_runs_twin(pl, nsteps) ? 1 : 0;
+  return PM_OK;
+}
+
 int pm_column_steps(const pm_columns *cols, const double *wA, const double *vdx_in,
                     const double *b_in, double dt, int32_t nsteps, int32_t ops,
                     int32_t lanes_per_col, pm_stream_t stream) {

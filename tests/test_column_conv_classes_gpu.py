@@ -12,7 +12,8 @@ and 1, the 70 + 70 split entering it again from the state the first launch left.
 Not covered in isolation: the block check's comparison of the surface's bit pattern.  A neighbour
 can only turn non-finite inside a speculative block by way of huge finite values, and a huge
 positive one convects first, which ends the block through the other test; with a non-finite
-level in the initial state the whole wave takes the IEEE form (case d)."""
+level in the initial state the whole wave takes the IEEE form (case d).  (A kernel without that
+comparison also passes tests/test_column_cls_churn_gpu.py: DESIGN.md, the mutants of the block check.)"""
 import numpy as np
 import pytest
 
@@ -25,6 +26,7 @@ AREA_PROVEN = 8e13                 # (the 2-instruction proof accepts it: assert
 AREA_REJECTED = 138681915977248.73  # (the 2-instruction proof rejects it: the Area leg takes 3)
 NZS = (9, 64, 65, 100, 128)         # P = 1, 1, 2, 2, 2 at 64 lanes per column
 LAUNCHES = {"70": (70,), "24": (24,), "33+37": (33, 37), "70+70": (70, 70)}
+LAUNCH_TWIN = {"70": True, "24": False, "33+37": False, "70+70": True}  # k_column_steps_cls runs it
 FORMS = ("form8", "form7", "form6")
 
 
@@ -224,7 +226,8 @@ def test_constructed_columns_vs_oracle(gpu, nz, group, launch, form):
     assert not batch.div2_area_proven.any() or form != "form7"
   if batch.div3_proven:
     assert "k_column_steps<64" in batch.kernel_name(chunks[0], lanes_per_col=64)
-  for n in chunks:
+  for n in chunks:  # which of the two kernels the launch runs (the module's docstring)
+    assert batch.kernel_twin(n, lanes_per_col=64) == LAUNCH_TWIN[launch]
     batch.steps(inp["wA"], DT, n, lanes_per_col=64)
   got = batch.get_b()
   ref = inp["ref"][sum(chunks)]

@@ -173,9 +173,13 @@ def test_convective_pattern_churn_vs_oracle(gpu, nz, G):
   do_conv = np.ones(n, bool)
   ref = O.column_ensemble_steps(z, kappa, area, b0, wA, dt, do_conv, bs, bbot, N2min, 400)
   batch = gpu.ColumnBatch(z, kappa, area, b0, bs=bs, bbot=bbot, N2min=N2min, do_conv=do_conv)
+  # (which kernel the case covers: one wave per column and at most 2 levels per lane, every Area one
+  # number -- the 400-step launch runs the twin k_column_steps_cls, the 50-step launches do not)
+  assert batch.kernel_twin(400, lanes_per_col=G) == (G == 0 and nz <= 128)
   batch.steps(wA, dt, 400, lanes_per_col=G)
   assert np.array_equal(batch.get_b(), ref, equal_nan=True)
   batch2 = gpu.ColumnBatch(z, kappa, area, b0, bs=bs, bbot=bbot, N2min=N2min, do_conv=do_conv)
+  assert not batch2.kernel_twin(50, lanes_per_col=G)
   for _ in range(8):
     batch2.steps(wA, dt, 50, lanes_per_col=G)
   assert np.array_equal(batch2.get_b(), ref, equal_nan=True)

@@ -558,6 +558,46 @@ def test_column_kernel_name_follows_the_launch_plan():
   assert buf.value == b"k_column_steps<64,1,0,false,false>"
 
 
+def test_column_kernel_twin_follows_the_launch():
+  """pm_column_kernel_twin: launches of at least 64 steps of the one-wave-per-column uniform-Area
+  rows with at most 2 levels per lane run k_column_steps_cls (launch_column_kernel asks the same
+  predicate); every other launch, and a call that launches nothing, does not.  The row's name stays
+  the one pm_column_kernel_name reports either way."""
+  from pymoc_amd import _lib
+  L, C = _lib.lib, ctypes
+  A = 0x10000
+  T, CT, PSI, TWO = _lib.PM_OP_TIMESTEP, _lib.PM_OP_CONTRACTED, _lib.PM_OP_WA_PSI, _lib.PM_OP_WA_TWOBASIN
+
+  def twin(ncols=1024, nz=100, nsteps=64, ops=T, ua=True, d3=True, vdx=None, lanes=0):
+    c = _lib.pm_columns()
+    c.ncols, c.nz, c.nsel = ncols, nz, 1
+    c.reserved = (_lib.PM_COLS_ALL_UNIFORM_AREA if ua else 0) | (_lib.PM_COLS_DIV3_PROVEN if d3 else 0)
+    c.z = c.b = c.kappa = c.area = c.dAkappa = c.bs = c.bbot = c.N2min = A
+    out, buf = C.c_int32(-1), C.create_string_buffer(96)
+    assert L.pm_column_kernel_twin(C.byref(c), A, vdx, nsteps, ops, lanes, C.byref(out)) == _lib.PM_OK
+    assert L.pm_column_kernel_name(C.byref(c), A, vdx, nsteps, ops, lanes, buf, 96) == _lib.PM_OK
+    assert "_cls" not in buf.value.decode()
+    return out.value
+
+  for kw, want in [
+      (dict(), 1), (dict(nsteps=63), 0), (dict(nsteps=65), 1), (dict(nsteps=1000, d3=False), 1),
+      (dict(nz=9), 1), (dict(nz=64), 1), (dict(nz=65), 1), (dict(nz=128), 1), (dict(nz=129), 0),
+      (dict(nz=256), 0), (dict(ua=False), 0), (dict(lanes=16), 0), (dict(lanes=32), 0),
+      (dict(lanes=64), 1), (dict(ops=T | CT), 0), (dict(vdx=A), 0), (dict(ops=T | PSI), 1),
+      (dict(ops=T | PSI, nsteps=24), 0), (dict(ops=T | TWO, ncols=3000, vdx=A), 1),
+      (dict(ops=T | TWO, ncols=3000, vdx=A, ua=False), 0), (dict(nsteps=2), 0),
+      (dict(nsteps=1, ncols=32768), 0), (dict(nsteps=0), 0), (dict(ncols=0), 0),
+      (dict(ops=_lib.PM_OP_VERTADVDIFF), 0)]:
+    assert twin(**kw) == want, kw
+  c = _lib.pm_columns()
+  c.ncols, c.nz, c.nsel = 4, 10, 1
+  out = C.c_int32(-1)
+  assert L.pm_column_kernel_twin(C.byref(c), A, None, 64, T, 0, C.byref(out)) == _lib.PM_EINVAL
+  c.z = c.b = c.kappa = c.area = c.dAkappa = c.bs = c.bbot = c.N2min = A
+  assert L.pm_column_kernel_twin(C.byref(c), A, None, 64, T, 0, None) == _lib.PM_EINVAL
+  assert L.pm_column_kernel_twin(C.byref(c), A, None, 64, T, 8, C.byref(out)) == _lib.PM_EINVAL
+
+
 def test_every_launch_plan_row_has_a_whole_batch_oracle_case():
   """tests/column_plan_cases.py, the table tests/test_column_plan_gpu.py runs on the device, holds
   every row of PM_COLUMN_KERNELS (a row added without a numeric case fails here), each entry's
