@@ -37,8 +37,9 @@ sys.path.insert(1, os.path.join(ROOT, "tests"))  # windows_cases, stats_cases: t
 import pymoc_amd
 from pymoc_amd import configs
 from pymoc_amd.device import DeviceArray, Event, LaunchTimer, synchronize
+from pymoc_amd.series import _Plane
 from pymoc_amd.steady import YEAR
-from pymoc_amd.windows import _Plane, _launch_kendall
+from pymoc_amd.windows import launch_kendall
 import stats_cases as STC
 import windows_cases as WC
 
@@ -203,9 +204,9 @@ def time_it(args):
     og = st._launch_group(0, nwin)
     synchronize()
     t_win = _median_ms(lambda: sw._launch(0, nrec, nwin, out=out), args.reps) - null
-    counts = _launch_kendall(_Plane(out[0], 3, shape), shape, 0, nwin, None, None)
-    kd = lambda: _launch_kendall(_Plane(out[0], 3, shape), shape, 0, nwin, None, None,  # noqa: E731
-                                 out=counts)
+    counts = launch_kendall(_Plane(out[0], 3, shape), shape, 0, nwin, None, None)
+    kd = lambda: launch_kendall(_Plane(out[0], 3, shape), shape, 0, nwin, None, None,  # noqa: E731
+                                out=counts)
     t_kd = _median_ms(kd, args.reps) - null
 
     def across():

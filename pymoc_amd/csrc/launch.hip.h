@@ -1,6 +1,7 @@
-// launch.hip.h -- the host side of a launch, shared by the launchers of the per-member kernels:
-// block sizing against the CU's LDS, the launch itself, row alignment, runtime flags as template
-// arguments.  Host code only, inline / templates throughout (compiled into two translation units).
+// launch.hip.h -- the host side of a launch, shared by the launchers of the per-member kernels and
+// of the series kernels: block sizing against the CU's LDS, the launch itself, row alignment,
+// runtime flags as template arguments.  Host code only, inline / templates throughout (compiled
+// into several translation units).
 #pragma once
 #include <type_traits>
 #include "common.hip.h"
@@ -36,13 +37,14 @@ inline int waves_per_block_fitting(size_t per_wave_bytes, size_t shared_bytes, i
 }
 
 // kernel<<<grid, block, lds_bytes, st>>>(args...), its dynamic-LDS limit raised first if need be
+// (a 1-D grid or block is given as a plain integer)
 template <class... P, class... A>
-int launch_dyn(void (*kernel)(P...), unsigned grid, unsigned block, size_t lds_bytes,
-               hipStream_t st, const A &...args) {
+int launch_dyn(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st,
+               const A &...args) {
   if (lds_bytes > LDS_DYN_UNRAISED)
     PM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds_bytes));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, st, args...);
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args...);
   PM_HIP(hipGetLastError());
   return PM_OK;
 }

@@ -37,6 +37,7 @@
 #include <cmath>
 #include "common.hip.h"
 #include "launch.hip.h"
+#include "series.hip.h"
 
 namespace pm {
 
@@ -57,10 +58,6 @@ struct SpGeom {
   // four, but below 128 VGPRs a thread the compiler spills to scratch)
   static constexpr int WAVES_PER_SIMD = L <= 256 ? 3 : 1;
 };
-
-__device__ __forceinline__ bool sp_finite(double x) {
-  return fabs(x) <= 1.7976931348623157e308;  // false for NaN and +-inf
-}
 
 // One butterfly of the definition: (u, v) <- (u + W v, u - W v), every product and sum rounded on
 // its own.
@@ -88,11 +85,10 @@ __device__ __forceinline__ void sp_transform(const double *__restrict__ v,
   const int tid = threadIdx.x;
   // rows of TM adjacent members, turned into one series per member, bit-reversed.  A thread keeps
   // its member (TM divides the block) and takes every (256 / TM)-th record; the loads of a chunk
-  // are issued together, free of branches, before the first of them is waited for.  A member past
-  // the end reads the last one's values: they are in bounds, and nothing of it is stored.
+  // are issued together, free of branches, before the first of them is waited for.
   constexpr int NL = TM * L / SP_THREADS, CH = NL < 8 ? NL : 8;
-  const int mi = tid % TM, mc = m0 + mi < n ? m0 + mi : n - 1;
-  const double *base = v + (size_t)kb * rs + (size_t)s * n + mc;
+  const int mi = tid % TM;
+  const double *base = series_row(v, rs, n, kb, s, m0, mi);
   bool fin = true;
 #pragma unroll 1
   for (int c = 0; c < NL; c += CH) {
@@ -104,7 +100,7 @@ __device__ __forceinline__ void sp_transform(const double *__restrict__ v,
     for (int u = 0; u < CH; ++u) {
       const int j = tid / TM + (c + u) * (SP_THREADS / TM);
       re[mi * LP + (int)(__brev((unsigned)j) >> (32 - G::LOG))] = x[u];
-      fin = fin && sp_finite(x[u]);
+      fin = fin && series_finite(x[u]);
     }
   }
   if (!fin) bad[mi] = 1;
@@ -305,17 +301,11 @@ int sp_launch(const struct pm_series_spectra &d, int nseg, hipStream_t st, int32
   using G = SpGeom<L>;
   static_assert(G::LDS <= LDS_PER_CU, "the tile does not fit the CU's LDS");
   static_assert(G::TM * 8 >= 64 && 4 * G::TM <= SP_THREADS, "tile rows of at least 64 bytes");
-  auto kernel = k_series_spectra<L>;
-  if (G::LDS > LDS_DYN_UNRAISED)
-    PM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)G::LDS));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((d.n + G::TM - 1) / G::TM),
-                                  (unsigned)(d.nspec + d.npairs)),
-                     dim3(SP_THREADS), G::LDS, st, d.v, d.window_dev, d.twiddle, d.pair_dev,
-                     (int)d.n, (int)d.nspec, (int)d.k0, nseg, (int)d.step, (int)d.detrend,
-                     (int)d.npairs, d.scale, nused, psd, nused_pair, csd);
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return launch_dyn(k_series_spectra<L>,
+                    dim3((unsigned)((d.n + G::TM - 1) / G::TM), (unsigned)(d.nspec + d.npairs)),
+                    SP_THREADS, G::LDS, st, d.v, d.window_dev, d.twiddle, d.pair_dev, (int)d.n,
+                    (int)d.nspec, (int)d.k0, nseg, (int)d.step, (int)d.detrend, (int)d.npairs,
+                    d.scale, nused, psd, nused_pair, csd);
 }
 
 }  // namespace pm
@@ -328,10 +318,7 @@ int pm_series_spectra(const struct pm_series_spectra *dp, int32_t *nused, double
                       int32_t *nused_pair, double *csd, pm_stream_t stream) {
   PM_REQUIRE(dp, "d is NULL");
   const struct pm_series_spectra &d = *dp;
-  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nrec >= 1, "n %d, nspec %d or nrec %d < 1", d.n,
-             d.nspec, d.nrec);
-  PM_REQUIRE(0 <= d.k0 && d.k0 < d.k1 && d.k1 <= d.nrec,
-             "window [%d, %d) is not inside the %d records", d.k0, d.k1, d.nrec);
+  PM_SERIES_REQUIRE(d);
   const int L = d.nperseg;
   PM_REQUIRE(L >= PM_SPEC_NPERSEG_MIN && L <= PM_SPEC_NPERSEG_MAX && (L & (L - 1)) == 0,
              "nperseg %d is not a power of two in [%d, %d]", L, PM_SPEC_NPERSEG_MIN,

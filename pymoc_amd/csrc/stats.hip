@@ -35,6 +35,7 @@
 #include <cmath>
 #include "common.hip.h"
 #include "launch.hip.h"
+#include "series.hip.h"
 
 namespace pm {
 
@@ -50,10 +51,6 @@ __device__ __forceinline__ unsigned long long st_key(double x) {
 __device__ __forceinline__ double st_unkey(unsigned long long k) {
   const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
   return __longlong_as_double((long long)u);
-}
-
-__device__ __forceinline__ bool st_finite(double x) {
-  return fabs(x) <= 1.7976931348623157e308;  // false for NaN and +-inf
 }
 
 // The value of lane (l ^ J).  Strides 1 and 2 are DPP quad permutations ([1,0,3,2] = 0xB1,
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_series_group_stats(
       const size_t rec = rec0 + p;
       const double x = xn;
       xn = (have && p + step < npairs) ? v[(rec + step) * (size_t)n + m] : __builtin_nan("");
-      const bool fin = have && st_finite(x);
+      const bool fin = have && series_finite(x);
       const int count = __popcll(__ballot(fin));
       const double sum = st_tree(0.0 + (fin ? x : 0.0));
       const double mean = sum / (double)count;
@@ -216,7 +213,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_series_group_stats(
     for (int j = threadIdx.x; j < G; j += GS_THREADS) {
       const double x = row[order[g0 + j]];
       lds[j] = (unsigned long long)__double_as_longlong(x);
-      mine += st_finite(x) ? 1 : 0;
+      mine += series_finite(x) ? 1 : 0;
     }
 #pragma unroll
     for (int s = WAVE / 2; s > 0; s >>= 1) mine += __shfl_xor(mine, s, WAVE);
@@ -229,14 +226,14 @@ __global__ __launch_bounds__(GS_THREADS) void k_series_group_stats(
       double pl = 0.0;
       for (int j = lane; j < G; j += WAVE) {
         const double x = __longlong_as_double((long long)lds[j]);
-        pl += st_finite(x) ? x : 0.0;
+        pl += series_finite(x) ? x : 0.0;
       }
       const double sum = st_tree(pl);
       const double mean = sum / (double)count;
       double ql = 0.0;
       for (int j = lane; j < G; j += WAVE) {
         const double x = __longlong_as_double((long long)lds[j]);
-        const double d = st_finite(x) ? x - mean : 0.0;
+        const double d = series_finite(x) ? x - mean : 0.0;
         ql += d * d;
       }
       const double Q = st_tree(ql);
@@ -253,7 +250,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_series_group_stats(
       unsigned long long key = KEY_LAST;
       if (j < G) {
         const double x = __longlong_as_double((long long)lds[j]);
-        if (st_finite(x)) key = st_key(x);
+        if (series_finite(x)) key = st_key(x);
       }
       lds[j] = key;
     }
@@ -308,7 +305,7 @@ __global__ __launch_bounds__(MS_TM * MS_TC) void k_series_member_stats(
   const double t = thr[s];
   const bool has_t = t == t;
   const bool below = dir[s] < 0;
-  auto hit = [&](double x) { return has_t && st_finite(x) && (below ? x < t : x > t); };
+  auto hit = [&](double x) { return has_t && series_finite(x) && (below ? x < t : x > t); };
 
   // pass 1: sum, count, extrema, threshold statistics
   double total = 0.0;
@@ -326,7 +323,7 @@ __global__ __launch_bounds__(MS_TM * MS_TC) void k_series_member_stats(
         // (the last record's successor: the record itself, read and discarded)
         const double xl = x0[(size_t)(k + 1 < k1 ? k + 1 : k) * rs];
         const double xn = k + 1 < k1 ? xl : __builtin_nan("");
-        const bool fin = st_finite(x);
+        const bool fin = series_finite(x);
         acc += fin ? x : 0.0;
         if (fin) {
           ++count;
@@ -337,7 +334,7 @@ __global__ __launch_bounds__(MS_TM * MS_TC) void k_series_member_stats(
             ++hits;
             first = k < first ? k : first;
           }
-          if (st_finite(xn) && h != hit(xn)) ++ncross;
+          if (series_finite(xn) && h != hit(xn)) ++ncross;
         }
         x = xn;
       }
@@ -389,7 +386,7 @@ __global__ __launch_bounds__(MS_TM * MS_TC) void k_series_member_stats(
 #pragma unroll 4
       for (int k = ka; k < kb; ++k) {
         const double x = x0[(size_t)k * rs];
-        const double d = st_finite(x) ? x - mean : 0.0;
+        const double d = series_finite(x) ? x - mean : 0.0;
         acc += d * d;
       }
       part[0][ty][tx] = acc;
@@ -403,7 +400,7 @@ __global__ __launch_bounds__(MS_TM * MS_TC) void k_series_member_stats(
 #pragma unroll 4
           for (int k = ka; k < ke; ++k) {
             const double x = x0[(size_t)k * rs], y = x0[(size_t)(k + L) * rs];
-            const bool ok = st_finite(x) && st_finite(y);
+            const bool ok = series_finite(x) && series_finite(y);
             a += ok ? (x - mean) * (y - mean) : 0.0;
             np += ok ? 1 : 0;
           }
@@ -456,10 +453,7 @@ int pm_series_group_stats(const struct pm_series_group_stats *dp, int32_t *count
                           pm_stream_t stream) {
   PM_REQUIRE(dp, "d is NULL");
   const struct pm_series_group_stats &d = *dp;
-  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nrec >= 1, "n %d, nspec %d or nrec %d < 1", d.n,
-             d.nspec, d.nrec);
-  PM_REQUIRE(0 <= d.k0 && d.k0 < d.k1 && d.k1 <= d.nrec,
-             "window [%d, %d) is not inside the %d records", d.k0, d.k1, d.nrec);
+  PM_SERIES_REQUIRE(d);
   PM_REQUIRE(d.ngroups >= 1, "ngroups %d < 1", d.ngroups);
   PM_REQUIRE((long long)(d.k1 - d.k0) * d.nspec < (1ll << 30),
              "(k1 - k0) * nspec = %lld is not below 2^30", (long long)(d.k1 - d.k0) * d.nspec);
@@ -519,10 +513,7 @@ int pm_series_member_stats(const struct pm_series_member_stats *dp, int32_t *cou
                            int32_t *ncross, double *stat, pm_stream_t stream) {
   PM_REQUIRE(dp, "d is NULL");
   const struct pm_series_member_stats &d = *dp;
-  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nrec >= 1, "n %d, nspec %d or nrec %d < 1", d.n,
-             d.nspec, d.nrec);
-  PM_REQUIRE(0 <= d.k0 && d.k0 < d.k1 && d.k1 <= d.nrec,
-             "window [%d, %d) is not inside the %d records", d.k0, d.k1, d.nrec);
+  PM_SERIES_REQUIRE(d);
   PM_REQUIRE(d.nlag >= 0 && d.nlag <= PM_STATS_LAG_MAX, "nlag %d outside [0, %d]", d.nlag,
              PM_STATS_LAG_MAX);
   PM_REQUIRE(d.nspec <= 65535, "nspec %d > 65535", d.nspec);

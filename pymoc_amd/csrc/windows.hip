@@ -32,14 +32,11 @@
 #include <cmath>
 #include "common.hip.h"
 #include "launch.hip.h"
+#include "series.hip.h"
 
 namespace pm {
 
 constexpr int WN_THREADS = 1024;
-
-__device__ __forceinline__ bool wn_finite(double x) {
-  return fabs(x) <= 1.7976931348623157e308;  // false for NaN and +-inf
-}
 
 // The tile of a launch: TM adjacent members (32, 16, 8 or 4) and at most R records of LDS -- half
 // a CU's LDS (two blocks to a CU) or all of it.  nwb = the windows a block takes: what fits R, a
@@ -107,8 +104,8 @@ __global__ __launch_bounds__(WN_THREADS) void k_series_windows(
   const size_t rs = (size_t)nspec * (size_t)n;            // doubles between records
   const int mi = tid & (TM - 1), slot = tid >> ltm, slots = WN_THREADS >> ltm;
 
-  // rows of TM adjacent members.  A member past the end reads the last one's values: they are in
-  // bounds, and nothing of it is stored.
+  // rows of TM adjacent members: series_row(v, rs, n, k0 + i0 * S, s, m0, mi), written out -- with
+  // the record formed before the clamp the compiler schedules this kernel differently
   {
     const int mc = m0 + mi < n ? m0 + mi : n - 1;
     const double *base = v + (size_t)(k0 + i0 * S) * rs + (size_t)s * n + mc;
@@ -131,7 +128,7 @@ __global__ __launch_bounds__(WN_THREADS) void k_series_windows(
 #pragma unroll 4
     for (int j = 0; j < W; ++j) {
       const double xj = xw[j << ltm];
-      fin = fin && wn_finite(xj);
+      fin = fin && series_finite(xj);
       sum = sum + xj;
       if (DET == PM_WIN_DETREND_LINEAR) {
         st = st + t * xj;
@@ -202,17 +199,11 @@ int wn_launch(const struct pm_series_windows &d, int nwin, hipStream_t st, doubl
              "member tiles * window chunks = %lld is not below 2^31", ntiles * nchunks);
   const int nw = nwin < g.nwb ? nwin : g.nwb;
   const size_t lds = wn_lds(g, d.window + (nw - 1) * d.step);
-  auto kernel = k_series_windows<DET, LAG1>;
-  if (lds > LDS_DYN_UNRAISED)
-    PM_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
   PM_HIP(hipMemsetAsync(nused, 0, sizeof(int32_t) * (size_t)d.nspec * (size_t)d.n, st));
-  hipLaunchKernelGGL(kernel, dim3((unsigned)(ntiles * nchunks), (unsigned)d.nspec),
-                     dim3(WN_THREADS), lds, st, d.v, (int)d.n, (int)d.nspec, (int)d.k0,
-                     (int)d.window, (int)d.step, (int)d.lag, nwin, g.nwb, nchunks, g.ltm, d.stt,
-                     out, nused);
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return launch_dyn(k_series_windows<DET, LAG1>,
+                    dim3((unsigned)(ntiles * nchunks), (unsigned)d.nspec), WN_THREADS, lds, st,
+                    d.v, (int)d.n, (int)d.nspec, (int)d.k0, (int)d.window, (int)d.step, (int)d.lag,
+                    nwin, g.nwb, nchunks, g.ltm, d.stt, out, nused);
 }
 
 // ------------------------------------------------------------------ K23
@@ -235,12 +226,11 @@ __global__ __launch_bounds__(WN_THREADS) void k_series_kendall(
   if (tid < 3 * TM) cnt[tid] = 0;
   int nfin = 0;
   {
-    const int mc = m0 + mi < n ? m0 + mi : n - 1;
-    const double *base = v + (size_t)k0 * rs + (size_t)s * n + mc;
+    const double *base = series_row(v, rs, n, k0, s, m0, mi);
 #pragma unroll 4
     for (int r = slot; r < K; r += slots) {
       const double xr = base[(size_t)r * rs];
-      const bool fin = wn_finite(xr);
+      const bool fin = series_finite(xr);
       nfin += fin ? 1 : 0;
       x[(r << ltm) + mi] = fin ? xr : nan;
     }
@@ -293,10 +283,7 @@ int pm_series_windows(const struct pm_series_windows *dp, double *out, int32_t *
                       pm_stream_t stream) {
   PM_REQUIRE(dp, "d is NULL");
   const struct pm_series_windows &d = *dp;
-  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nrec >= 1, "n %d, nspec %d or nrec %d < 1", d.n,
-             d.nspec, d.nrec);
-  PM_REQUIRE(0 <= d.k0 && d.k0 < d.k1 && d.k1 <= d.nrec,
-             "window [%d, %d) is not inside the %d records", d.k0, d.k1, d.nrec);
+  PM_SERIES_REQUIRE(d);
   const int W = d.window;
   PM_REQUIRE(W >= PM_WIN_MIN && W <= PM_WIN_MAX, "window length %d outside [%d, %d]", W,
              PM_WIN_MIN, PM_WIN_MAX);
@@ -334,10 +321,7 @@ int pm_series_kendall(const struct pm_series_kendall *dp, int32_t *conc, int32_t
                       int32_t *tie, int32_t *nfin, pm_stream_t stream) {
   PM_REQUIRE(dp, "d is NULL");
   const struct pm_series_kendall &d = *dp;
-  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nrec >= 1, "n %d, nspec %d or nrec %d < 1", d.n,
-             d.nspec, d.nrec);
-  PM_REQUIRE(0 <= d.k0 && d.k0 < d.k1 && d.k1 <= d.nrec,
-             "window [%d, %d) is not inside the %d records", d.k0, d.k1, d.nrec);
+  PM_SERIES_REQUIRE(d);
   const int K = d.k1 - d.k0;
   PM_REQUIRE(K <= PM_KENDALL_MAX, "the window [%d, %d) holds %d records, more than %d", d.k0, d.k1,
              K, PM_KENDALL_MAX);
@@ -347,15 +331,10 @@ int pm_series_kendall(const struct pm_series_kendall *dp, int32_t *conc, int32_t
   hipStream_t st = resolve_stream(stream);
   const int ltm = kd_ltm(K), tm = 1 << ltm;
   const size_t lds = sizeof(double) * (size_t)K * tm + sizeof(int) * 3 * tm;
-  if (lds > LDS_DYN_UNRAISED)
-    PM_HIP(hipFuncSetAttribute((const void *)k_series_kendall,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_series_kendall, dim3((unsigned)(((long long)d.n + tm - 1) / tm),
-                                            (unsigned)d.nspec),
-                     dim3(WN_THREADS), lds, st, d.v, (int)d.n, (int)d.nspec, (int)d.k0, K, ltm,
-                     conc, disc, tie, nfin);
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return launch_dyn(k_series_kendall,
+                    dim3((unsigned)(((long long)d.n + tm - 1) / tm), (unsigned)d.nspec),
+                    WN_THREADS, lds, st, d.v, (int)d.n, (int)d.nspec, (int)d.k0, K, ltm, conc,
+                    disc, tie, nfin);
 }
 
 }  // extern "C"

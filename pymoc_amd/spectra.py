@@ -17,7 +17,8 @@ A segment with a non-finite value is excluded and counted (`nused`), never propa
 transform is the iterative radix-2 decimation-in-time FFT with the op order include/pymoc_hip.h
 states, on a twiddle table made by `twiddles` alone, so every double equals the NumPy restatement
 (tests/spectra_cases.py) bit for bit; the restatement is pinned to scipy.signal.welch / csd
-(scaling="density", one-sided, detrend="constant" or False).
+(scaling="density", one-sided, detrend="constant" or False).  What a source and a record window
+[k0, k1) are: series.py.
 
 `coherence[(a, b)]` = |csd|^2 / (psd_a * psd_b) and `phase` = angle(csd) are formed on the host.
 The coherence needs the spectra of the pair's own segments; those are psd_a and psd_b exactly when
@@ -39,6 +40,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
+from .series import Series, as_int, by_name
 from .stats import SeriesStats
 
 _DETREND = dict(constant=_lib.PM_SPEC_DETREND_CONSTANT, none=_lib.PM_SPEC_DETREND_NONE)
@@ -82,26 +84,27 @@ class Spectra(object):
   def __init__(self, names, pairs, freq, nused, psd, nused_pair, csd):
     # psd [nf, nspec, n], csd [nf, 2 npairs, n]
     self.names, self.pairs, self.freq = list(names), list(pairs), freq
-    self.nused = {nm: nused[s] for s, nm in enumerate(names)}
-    self.psd = {nm: np.ascontiguousarray(psd[:, s, :].T) for s, nm in enumerate(names)}
-    self.csd, self.nused_pair, self.coherence, self.phase = {}, {}, {}, {}
+    self.nused, self.psd = by_name(names, nused), by_name(names, psd.transpose(1, 2, 0))
+    self.nused_pair = by_name(pairs, nused_pair)
+    self.csd = by_name(pairs, [(csd[:, 2 * p, :] + 1j * csd[:, 2 * p + 1, :]).T
+                               for p in range(len(pairs))])
+    coherence = []
     for p, (a, b) in enumerate(pairs):
-      c = np.ascontiguousarray((csd[:, 2 * p, :] + 1j * csd[:, 2 * p + 1, :]).T)
-      self.csd[(a, b)], self.nused_pair[(a, b)] = c, nused_pair[p]
       same = (nused_pair[p] > 0) & (self.nused[a] == nused_pair[p]) & (self.nused[b] == nused_pair[p])
       with np.errstate(all="ignore"):
-        mod = np.abs(c)  # (two ratios of order one: spectra of 1e+-300 neither overflow nor vanish)
+        # (two ratios of order one: spectra of 1e+-300 neither overflow nor vanish)
+        mod = np.abs(self.csd[(a, b)])
         coh = (mod / self.psd[a]) * (mod / self.psd[b])
-      self.coherence[(a, b)] = np.where(same[:, None], coh, np.nan)
-      self.phase[(a, b)] = np.angle(c)
+      coherence.append(np.where(same[:, None], coh, np.nan))
+    self.coherence = by_name(pairs, coherence)
+    self.phase = by_name(pairs, [np.angle(self.csd[pr]) for pr in pairs])
 
 
-class SeriesSpectra(object):
+class SeriesSpectra(Series):
   """`SeriesSpectra(source, nperseg, noverlap=None, window="hann", detrend="constant", pairs=(),
   dt_record=1.0, groups=None, stream=None)`.
 
-  source      an `IndexRecorder`, or `(DeviceArray [nrec, nspec, n], names)` for any device series
-              (`stream=` is then the stream the series is written on)
+  source      an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
   nperseg     L, a power of two in [8, 1024]
   noverlap    records two consecutive segments share, in [0, L - 1]; None: L // 2
   window      "hann" (periodic, as scipy.signal.get_window), "boxcar" or an array [L]
@@ -111,43 +114,19 @@ class SeriesSpectra(object):
   groups      int array [n] of labels, for `across_members` (as SeriesStats)
 
   Each call of `compute` / `across_members` is one launch of pm_series_spectra on the source's
-  stream.  With a recorder as source a window that holds a record never written is a ValueError."""
+  stream.  [k0, k1) is a record window (series.py) of at least nperseg records."""
 
   def __init__(self, source, nperseg, noverlap=None, window="hann", detrend="constant", pairs=(),
                dt_record=1.0, groups=None, stream=None):
-    self._rec = None
-    if isinstance(source, tuple):
-      if len(source) != 2:
-        raise ValueError("a source is an IndexRecorder or (DeviceArray [nrec, nspec, n], names)")
-      arr, names = source
-      self.stream = stream
-    else:
-      self._rec = source
-      arr, names = source._values, source.table.names
-      self.stream = source.ens.stream
-    shape = tuple(getattr(arr, "shape", ()))
-    if len(shape) != 3 or min(shape) < 1 or np.dtype(getattr(arr, "dtype", None)) != np.float64:
-      raise ValueError("the series must be a float64 device array [nrec, nspec, n] (shape %r here)"
-                       % (shape,))
-    self.nrec, self.nspec, self.n = shape
-    self.names = list(names)
-    if len(self.names) != self.nspec or len(set(self.names)) != self.nspec:
-      raise ValueError("the series has %d indices but %d distinct names are given"
-                       % (self.nspec, len(set(self.names))))
-    L = nperseg
-    if not isinstance(L, (int, np.integer)) or isinstance(L, bool):
-      raise ValueError("nperseg must be an integer (%r here)" % (L,))
-    L = int(L)
+    Series.__init__(self, source, stream)
+    L = as_int("nperseg", nperseg)
     if not _lib.PM_SPEC_NPERSEG_MIN <= L <= _lib.PM_SPEC_NPERSEG_MAX or L & (L - 1):
       raise ValueError("nperseg must be a power of two in [%d, %d] (%d here)"
                        % (_lib.PM_SPEC_NPERSEG_MIN, _lib.PM_SPEC_NPERSEG_MAX, L))
-    if noverlap is None:
-      noverlap = L // 2
-    if not isinstance(noverlap, (int, np.integer)) or isinstance(noverlap, bool):
-      raise ValueError("noverlap must be an integer (%r here)" % (noverlap,))
+    noverlap = L // 2 if noverlap is None else as_int("noverlap", noverlap)
     if not 0 <= noverlap <= L - 1:
       raise ValueError("noverlap must lie in [0, nperseg - 1 = %d] (%d here)" % (L - 1, noverlap))
-    self.nperseg, self.noverlap, self.step, self.nf = L, int(noverlap), L - int(noverlap), L // 2 + 1
+    self.nperseg, self.noverlap, self.step, self.nf = L, noverlap, L - noverlap, L // 2 + 1
     if isinstance(window, str):
       if window not in ("hann", "boxcar"):
         raise ValueError("unknown window %r (one of hann, boxcar, or an array [nperseg])"
@@ -195,35 +174,18 @@ class SeriesSpectra(object):
                        % (self.nspec + len(pairs)))
     self.pairs, self.detrend, self.dt_record = pairs, detrend, dt
     self.freq = np.arange(self.nf, dtype=np.float64) / (L * dt)
-    self.groups = groups
-    if groups is not None:  # checked now, used by across_members
-      SeriesStats((arr, self.names), groups=groups)
+    self._set_groups(groups)  # checked now, used by across_members
     # host mirrors (the entry checks these) and, from the first launch on, device copies
-    self._series, self._w, self._tw, self._pair, self._scale = arr, w, twiddles(L), idx, float(scale)
+    self._w, self._pair, self._scale = w, idx, float(scale)
+    self._host = dict(w=w, tw=twiddles(L), pair=idx)
     self.window, self.scale = w.copy(), float(scale)
-    self._dev = None
 
   # ------------------------------------------------------------------ device side
-  def _upload(self):
-    if self._dev is None:
-      s = self.stream
-      up = lambda a: DeviceArray.from_host(a, dtype=a.dtype, stream=s)  # noqa: E731
-      self._dev = dict(w=up(self._w), tw=up(self._tw), pair=up(self._pair))
-    return self._dev
-
   def _window(self, k0, k1):
-    k0 = int(k0)
-    k1 = self.nrec if k1 is None else int(k1)
-    if not 0 <= k0 < k1 <= self.nrec:
-      raise ValueError("window [%d, %d) is not inside the %d records" % (k0, k1, self.nrec))
+    k0, k1 = self._record_window(k0, k1)
     if k1 - k0 < self.nperseg:
       raise ValueError("window [%d, %d) holds %d records, fewer than nperseg = %d"
                        % (k0, k1, k1 - k0, self.nperseg))
-    if self._rec is not None:
-      missing = np.nonzero(self._rec.steps[k0:k1] < 0)[0]
-      if missing.size:
-        raise ValueError("window [%d, %d) holds record %d, which was never written"
-                         % (k0, k1, k0 + missing[0]))
     return k0, k1
 
   def nseg(self, k0=0, k1=None):
@@ -231,8 +193,13 @@ class SeriesSpectra(object):
     k0, k1 = self._window(k0, k1)
     return (k1 - k0 - self.nperseg) // self.step + 1
 
-  def _timer(self):
-    return self._rec.ens.timer if self._rec is not None else None
+  def _alloc(self, npairs):
+    """The outputs of a launch with `npairs` pairs: (nused, psd, nused_pair, csd), the last two
+    None without pairs."""
+    return (DeviceArray((self.nspec, self.n), np.int32),
+            DeviceArray((self.nf, self.nspec, self.n), np.float64),
+            DeviceArray((npairs, self.n), np.int32) if npairs else None,
+            DeviceArray((self.nf, 2 * npairs, self.n), np.float64) if npairs else None)
 
   def _launch(self, k0, k1, out=None, npairs=None):
     """The launch alone: (nused, psd, nused_pair, csd) on the device, nothing synchronised.  `out`:
@@ -246,10 +213,7 @@ class SeriesSpectra(object):
                                               dev["tw"].ptr)
     d.pair, d.pair_dev, d.scale = self._pair.ctypes.data, dev["pair"].ptr, self._scale
     if out is None:
-      out = (DeviceArray((self.nspec, self.n), np.int32),
-             DeviceArray((self.nf, self.nspec, self.n), np.float64),
-             DeviceArray((npairs, self.n), np.int32) if npairs else None,
-             DeviceArray((self.nf, 2 * npairs, self.n), np.float64) if npairs else None)
+      out = self._alloc(npairs)
     with launch_span(self._timer(), "k_series_spectra", self.stream):
       check(lib.pm_series_spectra(C.byref(d), out[0].ptr, out[1].ptr,
                                   out[2].ptr if npairs else None, out[3].ptr if npairs else None,
@@ -270,8 +234,7 @@ class SeriesSpectra(object):
     [nq, ngroups, nf]).  A member with no used segment has a NaN spectrum: SeriesStats excludes
     and counts it."""
     k0, k1 = self._window(k0, k1)
-    out = (DeviceArray((self.nspec, self.n), np.int32),
-           DeviceArray((self.nf, self.nspec, self.n), np.float64), None, None)
+    out = self._alloc(0)
     # (its argument checks come before the launch)
     st = SeriesStats((out[1], self.names), groups=self.groups, quantiles=quantiles,
                      stream=self.stream)

@@ -16,7 +16,8 @@ per call (csrc/stats.hip) -- and downloads the results only; the series is never
 
 Non-finite values (members that blew up) are excluded and counted, never propagated.  Every sum
 has one order, stated in include/pymoc_hip.h and independent of the launch geometry, so each
-double equals its NumPy restatement (tests/stats_cases.py) bit for bit.
+double equals its NumPy restatement (tests/stats_cases.py) bit for bit.  What a source and a record
+window [k0, k1) are: series.py.
 
 Out of scope:
   * statistics across ranks: every rank reduces its own members, so a group must lie on one rank.
@@ -32,6 +33,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
+from .series import Series, by_name
 
 _DIRS = dict(below=-1, above=1)
 
@@ -61,21 +63,6 @@ def group_order(groups, n):
   return labels, order, start
 
 
-class _Named(object):
-  """`result.mean[name]`: the rows of one index."""
-
-  def __init__(self, names, arr, axis):
-    self._names, self._arr, self._axis = names, arr, axis
-
-  def __getitem__(self, name):
-    if name not in self._names:
-      raise KeyError("unknown index %r (one of %s)" % (name, ", ".join(self._names)))
-    return np.take(self._arr, self._names.index(name), axis=self._axis)
-
-  def keys(self):
-    return list(self._names)
-
-
 class GroupStats(object):
   """What `across_members` returns: count, mean, var, min, max, sum [ngroups, k1 - k0] and
   quantile [nq, ngroups, k1 - k0], each indexed by index name."""
@@ -83,10 +70,10 @@ class GroupStats(object):
   def __init__(self, names, count, stat, nq):
     # count [K, nspec, ngroups], stat [K, nspec, ngroups, 5 + nq]
     self.names = list(names)
-    self.count = _Named(self.names, count.transpose(1, 2, 0), 0)
+    self.count = by_name(self.names, count.transpose(1, 2, 0))
     for i, key in enumerate(("mean", "var", "min", "max", "sum")):
-      setattr(self, key, _Named(self.names, stat[..., i].transpose(1, 2, 0), 0))
-    self.quantile = _Named(self.names, stat[..., 5:5 + nq].transpose(1, 3, 2, 0), 0)
+      setattr(self, key, by_name(self.names, stat[..., i].transpose(1, 2, 0)))
+    self.quantile = by_name(self.names, stat[..., 5:5 + nq].transpose(1, 3, 2, 0))
 
 
 class MemberStats(object):
@@ -95,47 +82,27 @@ class MemberStats(object):
 
   def __init__(self, names, count, first, ncross, stat, nlag):
     self.names = list(names)
-    self.count, self.first = _Named(self.names, count, 0), _Named(self.names, first, 0)
-    self.ncross = _Named(self.names, ncross, 0)
+    self.count, self.first = by_name(self.names, count), by_name(self.names, first)
+    self.ncross = by_name(self.names, ncross)
     for i, key in enumerate(("mean", "var", "min", "max", "sum", "frac")):
-      setattr(self, key, _Named(self.names, stat[..., i], 0))
-    self.autocov = _Named(self.names, stat[..., 6:6 + nlag].transpose(0, 2, 1), 0)
+      setattr(self, key, by_name(self.names, stat[..., i]))
+    self.autocov = by_name(self.names, stat[..., 6:6 + nlag].transpose(0, 2, 1))
 
 
-class SeriesStats(object):
+class SeriesStats(Series):
   """`SeriesStats(source, groups=None, quantiles=(), lags=(), thresholds=None)`.
 
-  source      an `IndexRecorder`, or `(DeviceArray [nrec, nspec, n], names)` for any device series
-              (`stream=` is then the stream the series is written on)
+  source      an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
   groups      int array [n] of arbitrary labels (`group_labels`: ascending); None: one group
   quantiles   up to 8 probabilities in [0, 1]
   lags        up to 4 lags >= 1, in records
   thresholds  {name: (value, "below" | "above")}
 
   Each call of `across_members` / `along_time` is one launch on the source's stream, behind the
-  recorder's samples, and the download of the results.  With a recorder as source a window that
-  holds a record never written (`rec.steps == -1`) is a ValueError."""
+  recorder's samples, and the download of the results.  [k0, k1) is a record window (series.py)."""
 
   def __init__(self, source, groups=None, quantiles=(), lags=(), thresholds=None, stream=None):
-    self._rec = None
-    if isinstance(source, tuple):
-      if len(source) != 2:
-        raise ValueError("a source is an IndexRecorder or (DeviceArray [nrec, nspec, n], names)")
-      arr, names = source
-      self.stream = stream
-    else:
-      self._rec = source
-      arr, names = source._values, source.table.names
-      self.stream = source.ens.stream
-    shape = tuple(getattr(arr, "shape", ()))
-    if len(shape) != 3 or min(shape) < 1 or np.dtype(getattr(arr, "dtype", None)) != np.float64:
-      raise ValueError("the series must be a float64 device array [nrec, nspec, n] (shape %r here)"
-                       % (shape,))
-    self.nrec, self.nspec, self.n = shape
-    self.names = list(names)
-    if len(self.names) != self.nspec or len(set(self.names)) != self.nspec:
-      raise ValueError("the series has %d indices but %d distinct names are given"
-                       % (self.nspec, len(set(self.names))))
+    Series.__init__(self, source, stream)
     self.group_labels, order, start = group_order(groups, self.n)
     self.ngroups = start.size - 1
     q = np.atleast_1d(np.asarray(quantiles, dtype=np.float64))
@@ -164,39 +131,15 @@ class SeriesStats(object):
       if not np.isfinite(value):
         raise ValueError("threshold %r: the value must be finite (%r here)" % (name, value))
       thr[self.names.index(name)], dirs[self.names.index(name)] = float(value), _DIRS[side]
-    # host mirrors (the entries check these) and, from here on, device copies
-    self._series, self._q, self._lag = arr, q, lg.astype(np.int32)
+    # host mirrors (the entries check these) and, from the first launch on, device copies
+    self._q, self._lag = q, lg.astype(np.int32)
     self._start, self._order, self._thr, self._dir = start, order, thr, dirs
     self.quantiles, self.lags = q.copy(), self._lag.copy()
-    self._dev = None
+    one = np.zeros(1)
+    self._host = dict(order=order, start=start, q=q if q.size else one,
+                      lag=self._lag if lg.size else one.astype(np.int32), thr=thr, dir=dirs)
 
   # ------------------------------------------------------------------ device side
-  def _upload(self):
-    if self._dev is None:
-      s = self.stream
-      up = lambda a: DeviceArray.from_host(a, dtype=a.dtype, stream=s)  # noqa: E731
-      one = np.zeros(1)
-      self._dev = dict(order=up(self._order), start=up(self._start),
-                       q=up(self._q if self._q.size else one),
-                       lag=up(self._lag if self._lag.size else one.astype(np.int32)),
-                       thr=up(self._thr), dir=up(self._dir))
-    return self._dev
-
-  def _window(self, k0, k1, min_len=1):
-    k0 = int(k0)
-    k1 = self.nrec if k1 is None else int(k1)
-    if not 0 <= k0 < k1 <= self.nrec:
-      raise ValueError("window [%d, %d) is not inside the %d records" % (k0, k1, self.nrec))
-    if self._rec is not None:
-      missing = np.nonzero(self._rec.steps[k0:k1] < 0)[0]
-      if missing.size:
-        raise ValueError("window [%d, %d) holds record %d, which was never written"
-                         % (k0, k1, k0 + missing[0]))
-    return k0, k1
-
-  def _timer(self):
-    return self._rec.ens.timer if self._rec is not None else None
-
   def _launch_group(self, k0, k1, out=None):
     """The launch of `across_members` alone: (count, stat) on the device, nothing synchronised.
     `out`: the pair of an earlier call on the same window, written again."""
@@ -215,7 +158,7 @@ class SeriesStats(object):
     return count, stat
 
   def across_members(self, k0=0, k1=None):
-    k0, k1 = self._window(k0, k1)
+    k0, k1 = self._record_window(k0, k1)
     count, stat = self._launch_group(k0, k1)
     return GroupStats(self.names, count.download(stream=self.stream),
                       stat.download(stream=self.stream), self._q.size)
@@ -238,7 +181,7 @@ class SeriesStats(object):
     return ints, stat
 
   def along_time(self, k0=0, k1=None):
-    k0, k1 = self._window(k0, k1)
+    k0, k1 = self._record_window(k0, k1)
     if self._lag.size and self._lag.max() >= k1 - k0:
       raise ValueError("lag %d does not fit a window of %d records" % (self._lag.max(), k1 - k0))
     ints, stat = self._launch_member(k0, k1)

@@ -24,7 +24,8 @@ is per window, two sequential passes with the op order include/pymoc_hip.h state
 equals the NumPy restatement (tests/windows_cases.py) bit for bit; the Kendall counts are exact
 integers.  `ac` is the biased autocorrelation estimate (R's acf, statsmodels), not the Pearson
 correlation of the shifted pair (pandas.Series.autocorr).  An indicator is dated at the END of its
-window (`record_end`), the early-warning convention.
+window (`record_end`), the early-warning convention.  What a source and a record window [k0, k1)
+are: series.py.
 
 Out of scope:
   * Gaussian-kernel detrending;
@@ -42,6 +43,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
+from .series import Series, _Plane, as_int, by_name
 from .stats import SeriesStats
 
 _DETREND = dict(linear=_lib.PM_WIN_DETREND_LINEAR, constant=_lib.PM_WIN_DETREND_CONSTANT,
@@ -64,44 +66,16 @@ def tau_b(conc, disc, tie):
     return (conc - disc) / np.sqrt(n0 * (n0 - tie))
 
 
-def _source(source, stream):
-  """(recorder or None, array, names, stream, (nrec, nspec, n)) of a source, checked as SeriesStats
-  checks it."""
-  rec = None
-  if isinstance(source, tuple):
-    if len(source) != 2:
-      raise ValueError("a source is an IndexRecorder or (DeviceArray [nrec, nspec, n], names)")
-    arr, names = source
-  else:
-    rec = source
-    arr, names, stream = source._values, source.table.names, source.ens.stream
-  shape = tuple(getattr(arr, "shape", ()))
-  if len(shape) != 3 or min(shape) < 1 or np.dtype(getattr(arr, "dtype", None)) != np.float64:
-    raise ValueError("the series must be a float64 device array [nrec, nspec, n] (shape %r here)"
-                     % (shape,))
-  names = list(names)
-  if len(names) != shape[1] or len(set(names)) != shape[1]:
-    raise ValueError("the series has %d indices but %d distinct names are given"
-                     % (shape[1], len(set(names))))
-  if shape[1] > 65535:
-    raise ValueError("nspec = %d is above 65535" % shape[1])
-  return rec, arr, names, stream, shape
+class _Source(Series):
+  """A source as the two kernels of this module take it: at most 65535 indices."""
+
+  def __init__(self, source, stream=None):
+    Series.__init__(self, source, stream)
+    if self.nspec > 65535:
+      raise ValueError("nspec = %d is above 65535" % self.nspec)
 
 
-def _record_window(rec, nrec, k0, k1):
-  k0 = int(k0)
-  k1 = nrec if k1 is None else int(k1)
-  if not 0 <= k0 < k1 <= nrec:
-    raise ValueError("window [%d, %d) is not inside the %d records" % (k0, k1, nrec))
-  if rec is not None:
-    missing = np.nonzero(rec.steps[k0:k1] < 0)[0]
-    if missing.size:
-      raise ValueError("window [%d, %d) holds record %d, which was never written"
-                       % (k0, k1, k0 + missing[0]))
-  return k0, k1
-
-
-def _launch_kendall(arr, shape, k0, k1, stream, timer, out=None):
+def launch_kendall(arr, shape, k0, k1, stream, timer, out=None):
   """pm_series_kendall over the records [k0, k1) of a device series: the four int32 [nspec, n]
   count arrays on the device, nothing synchronised.  `out`: the arrays of an earlier call, written
   again."""
@@ -122,22 +96,21 @@ class Trend(object):
 
   def __init__(self, names, conc, disc, tie, nfin):
     self.names = list(names)
-    self.conc, self.disc, self.tie, self.nfin = ({nm: a[s] for s, nm in enumerate(self.names)}
+    self.conc, self.disc, self.tie, self.nfin = (by_name(self.names, a)
                                                  for a in (conc, disc, tie, nfin))
-    self.tau = {nm: tau_b(self.conc[nm], self.disc[nm], self.tie[nm]) for nm in self.names}
+    self.tau = by_name(self.names, tau_b(conc, disc, tie))
 
 
 def kendall(source, k0=0, k1=None, stream=None):
   """The `Trend` of any device series over the records [k0, k1) (at most 4096 of them): one launch
   of pm_series_kendall and the download of the counts.  `source` as for `SeriesWindows`."""
-  rec, arr, names, stream, shape = _source(source, stream)
-  k0, k1 = _record_window(rec, shape[0], k0, k1)
+  src = _Source(source, stream)
+  k0, k1 = src._record_window(k0, k1)
   if k1 - k0 > _lib.PM_KENDALL_MAX:
     raise ValueError("window [%d, %d) holds %d records, more than %d"
                      % (k0, k1, k1 - k0, _lib.PM_KENDALL_MAX))
-  timer = rec.ens.timer if rec is not None else None
-  out = _launch_kendall(arr, shape, k0, k1, stream, timer)
-  return Trend(names, *(a.download(stream=stream) for a in out))
+  out = launch_kendall(src._series, (src.nrec, src.nspec, src.n), k0, k1, src.stream, src._timer())
+  return Trend(src.names, *(a.download(stream=src.stream) for a in out))
 
 
 class Windows(object):
@@ -148,9 +121,8 @@ class Windows(object):
     # out [4, nwin, nspec, n]
     self.names, self.record_end = list(names), record_end
     for i, key in enumerate(INDICATORS):
-      setattr(self, key, {nm: np.ascontiguousarray(out[i, :, s, :].T)
-                          for s, nm in enumerate(self.names)})
-    self.nused = {nm: nused[s] for s, nm in enumerate(self.names)}
+      setattr(self, key, by_name(self.names, out[i].transpose(1, 2, 0)))
+    self.nused = by_name(self.names, nused)
 
 
 class WindowTrend(object):
@@ -160,11 +132,10 @@ class WindowTrend(object):
     self.var, self.ac = var, ac
 
 
-class SeriesWindows(object):
+class SeriesWindows(_Source):
   """`SeriesWindows(source, window, step=1, detrend="linear", lag=1, groups=None, stream=None)`.
 
-  source    an `IndexRecorder`, or `(DeviceArray [nrec, nspec, n], names)` for any device series
-            (`stream=` is then the stream the series is written on)
+  source    an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
   window    W, the records of a window, in [4, 4096]; any integer
   step      S, the records between the starts of two consecutive windows, in [1, W]
   detrend   "linear" (the window's least-squares line is removed), "constant" (its mean) or "none"
@@ -172,16 +143,12 @@ class SeriesWindows(object):
   groups    int array [n] of labels, for `across_members` (as SeriesStats)
 
   Each call of `compute` / `across_members` / `trend` is one launch of pm_series_windows on the
-  source's stream (and what follows it on the device).  With a recorder as source a record window
-  that holds a record never written is a ValueError."""
+  source's stream (and what follows it on the device).  [k0, k1) is a record window (series.py)
+  of at least W records."""
 
   def __init__(self, source, window, step=1, detrend="linear", lag=1, groups=None, stream=None):
-    self._rec, arr, self.names, self.stream, shape = _source(source, stream)
-    self.nrec, self.nspec, self.n = shape
-    for what, val in (("window", window), ("step", step), ("lag", lag)):
-      if not isinstance(val, (int, np.integer)) or isinstance(val, bool):
-        raise ValueError("%s must be an integer (%r here)" % (what, val))
-    W, S, Lg = int(window), int(step), int(lag)
+    _Source.__init__(self, source, stream)
+    W, S, Lg = as_int("window", window), as_int("step", step), as_int("lag", lag)
     if not _lib.PM_WIN_MIN <= W <= _lib.PM_WIN_MAX:
       raise ValueError("window must lie in [%d, %d] (%d here)"
                        % (_lib.PM_WIN_MIN, _lib.PM_WIN_MAX, W))
@@ -193,13 +160,10 @@ class SeriesWindows(object):
       raise ValueError("unknown detrend %r (one of linear, constant, none)" % (detrend,))
     self.window, self.step, self.lag, self.detrend = W, S, Lg, detrend
     self.stt = stt_of(W)
-    self.groups = groups
-    if groups is not None:  # checked now, used by across_members
-      SeriesStats((arr, self.names), groups=groups)
-    self._series = arr
+    self._set_groups(groups)  # checked now, used by across_members
 
   def _window(self, k0, k1):
-    k0, k1 = _record_window(self._rec, self.nrec, k0, k1)
+    k0, k1 = self._record_window(k0, k1)
     if k1 - k0 < self.window:
       raise ValueError("window [%d, %d) holds %d records, fewer than the window length %d"
                        % (k0, k1, k1 - k0, self.window))
@@ -217,8 +181,10 @@ class SeriesWindows(object):
     k0, k1, nwin = self._window(k0, k1)
     return k0 + np.arange(nwin) * self.step + self.window - 1
 
-  def _timer(self):
-    return self._rec.ens.timer if self._rec is not None else None
+  def _alloc(self, nwin):
+    """The outputs of a launch over `nwin` windows: (out [4, nwin, nspec, n], nused [nspec, n])."""
+    return (DeviceArray((4, nwin, self.nspec, self.n), np.float64),
+            DeviceArray((self.nspec, self.n), np.int32))
 
   def _launch(self, k0, k1, nwin, out=None):
     """The launch alone: (out [4, nwin, nspec, n], nused [nspec, n]) on the device, nothing
@@ -228,8 +194,7 @@ class SeriesWindows(object):
     d.window, d.step, d.lag, d.detrend = self.window, self.step, self.lag, _DETREND[self.detrend]
     d.v, d.stt = self._series.ptr, self.stt
     if out is None:
-      out = (DeviceArray((4, nwin, self.nspec, self.n), np.float64),
-             DeviceArray((self.nspec, self.n), np.int32))
+      out = self._alloc(nwin)
     with launch_span(self._timer(), "k_series_windows", self.stream):
       check(lib.pm_series_windows(C.byref(d), out[0].ptr, out[1].ptr, _sh(self.stream)))
     return out
@@ -248,8 +213,7 @@ class SeriesWindows(object):
     if which not in INDICATORS:
       raise ValueError("unknown indicator %r (one of %s)" % (which, ", ".join(INDICATORS)))
     k0, k1, nwin = self._window(k0, k1)
-    out = (DeviceArray((4, nwin, self.nspec, self.n), np.float64),
-           DeviceArray((self.nspec, self.n), np.int32))
+    out = self._alloc(nwin)
     # (its argument checks come before the launch)
     view = _Plane(out[0], INDICATORS.index(which), (nwin, self.nspec, self.n))
     st = SeriesStats((view, self.names), groups=self.groups, quantiles=quantiles,
@@ -270,15 +234,7 @@ class SeriesWindows(object):
     shape = (nwin, self.nspec, self.n)
     res = []
     for i in (2, 3):
-      cnt = _launch_kendall(_Plane(out, i, shape), shape, 0, nwin, self.stream, self._timer())
+      cnt = launch_kendall(_Plane(out, i, shape), shape, 0, nwin, self.stream, self._timer())
       res.append(Trend(self.names, *(a.download(stream=self.stream) for a in cnt)))
     return WindowTrend(*res)
 
-
-class _Plane(object):
-  """out[i] of a device array out[4][nwin][nspec][n] as a device series of its own: an address, a
-  shape and a dtype (the parent owns the memory and is kept alive)."""
-
-  def __init__(self, parent, i, shape):
-    self._parent, self.shape, self.dtype = parent, tuple(shape), np.dtype(np.float64)
-    self.ptr = parent.ptr + 8 * i * int(np.prod(shape))

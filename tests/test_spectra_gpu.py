@@ -8,48 +8,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from series_harness import I_SENTINEL, V_SENTINEL, _bits, _collect, _out, _padded, _up
 import spectra_cases as SC
 
 pytestmark = pytest.mark.gpu
-
-V_SENTINEL, I_SENTINEL = -7.25, -77
-PAD = 97    # doubles on either side of the series inside its allocation
-SPARE = 33  # elements behind every output
-
-
-def _bits(got, want, what, zero_sign=True):
-  """Bit for bit, NaN <-> NaN (any payload); zero_sign=False: -0.0 and +0.0 are the same."""
-  got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-  assert got.shape == want.shape, (what, got.shape, want.shape)
-  gn, wn = np.isnan(got), np.isnan(want)
-  assert np.array_equal(gn, wn), (what, "NaN pattern", np.argwhere(gn != wn)[:5])
-  same = got.view(np.uint64) == want.view(np.uint64)
-  if not zero_sign:
-    same |= (got == 0.0) & (want == 0.0)
-  bad = np.argwhere(~(same | gn))
-  assert bad.size == 0, (what, bad[:5], got[tuple(bad[0])], want[tuple(bad[0])])
-
-
-def _up(gpu, a):
-  return gpu.DeviceArray.from_host(a, dtype=a.dtype)
-
-
-def _padded(gpu, v):
-  """The series inside a larger allocation whose padding alternates NaN with 7e30: a segment with
-  a NaN is skipped by definition, so of a read outside the series it is the finite half that
-  shows."""
-  v = np.ascontiguousarray(v, dtype=np.float64)
-  buf = np.full(v.size + 2 * PAD, np.nan)
-  buf[0:PAD:2] = 7e30
-  buf[PAD + v.size::2] = 7e30
-  buf[PAD:PAD + v.size] = v.ravel()
-  return gpu.DeviceArray.from_host(buf)
-
-
-def _out(gpu, shape, dtype, sentinel):
-  size = int(np.prod(shape))
-  return _up(gpu, np.full(size + SPARE, sentinel, dtype=dtype)), size
-
 
 def run(gpu, c, v=None, pairs=None):
   """One launch of the case's settings (on another series / other pairs if given) into
@@ -60,7 +22,7 @@ def run(gpu, c, v=None, pairs=None):
   pairs = c["pairs"] if pairs is None else pairs
   nrec, nspec, n = v.shape
   L, nf, npairs = c["L"], c["L"] // 2 + 1, len(pairs)
-  series = _padded(gpu, v)
+  series, v_ptr = _padded(gpu, v)
   w = np.ascontiguousarray(c["w"], dtype=np.float64)
   pr = np.ascontiguousarray(pairs if npairs else [[0, 0]], dtype=np.int32)
   d_w, d_tw, d_pr = _up(gpu, w), _up(gpu, twiddles(L)), _up(gpu, pr)
@@ -72,18 +34,13 @@ def run(gpu, c, v=None, pairs=None):
   d.n, d.nspec, d.nrec, d.k0, d.k1 = n, nspec, nrec, c["k0"], c["k1"]
   d.nperseg, d.step, d.npairs = L, L - c["noverlap"], npairs
   d.detrend = dict(constant=_lib.PM_SPEC_DETREND_CONSTANT, none=_lib.PM_SPEC_DETREND_NONE)[c["detrend"]]
-  d.v, d.window, d.window_dev, d.twiddle = series.ptr + 8 * PAD, w.ctypes.data, d_w.ptr, d_tw.ptr
+  d.v, d.window, d.window_dev, d.twiddle = v_ptr, w.ctypes.data, d_w.ptr, d_tw.ptr
   d.pair, d.pair_dev, d.scale = pr.ctypes.data, d_pr.ptr, c["scale"]
   ptr = lambda k: out[k][0].ptr if (npairs or k in ("nused", "psd")) else None  # noqa: E731
   _lib.check(_lib.lib.pm_series_spectra(C.byref(d), ptr("nused"), ptr("psd"), ptr("nused_pair"),
                                         ptr("csd"), None))
   gpu.synchronize()
-  res = {}
-  for k, (dev, size) in out.items():
-    flat = dev.download().ravel()
-    assert (flat[size:] == shapes[k][2]).all(), (c["name"], k, "behind the output")
-    res[k] = flat[:size].reshape(shapes[k][0])
-  return res
+  return _collect(out, shapes, c["name"])
 
 
 def _same(got, want, what):

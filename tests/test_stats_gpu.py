@@ -7,49 +7,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from series_harness import I_SENTINEL, V_SENTINEL, _bits, _padded, _up
 import stats_cases as SC
 
 pytestmark = pytest.mark.gpu
-
-V_SENTINEL, I_SENTINEL = -7.25, -77
-PAD = 97  # doubles on either side of the series inside its allocation
-
-
-def _bits(got, want, what):
-  """Bit for bit, NaN <-> NaN (any payload), signed zeros as they are."""
-  got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-  assert got.shape == want.shape, (what, got.shape, want.shape)
-  gn, wn = np.isnan(got), np.isnan(want)
-  assert np.array_equal(gn, wn), (what, "NaN pattern", np.argwhere(gn != wn)[:5])
-  same = got.view(np.uint64) == want.view(np.uint64)
-  bad = np.argwhere(~(same | gn))
-  assert bad.size == 0, (what, bad[:5], got[tuple(bad[0])], want[tuple(bad[0])])
-
-
-class _Padded(object):
-  """The series inside a larger allocation.  The padding alternates NaN with 7e30: the kernels
-  skip a NaN by definition, so of a read outside the series it is the finite half that shows."""
-
-  def __init__(self, gpu, v):
-    v = np.ascontiguousarray(v, dtype=np.float64)
-    buf = np.full(v.size + 2 * PAD, np.nan)
-    buf[0:PAD:2] = 7e30
-    buf[PAD + v.size::2] = 7e30
-    buf[PAD:PAD + v.size] = v.ravel()
-    self.dev = gpu.DeviceArray.from_host(buf)
-    self.ptr = self.dev.ptr + 8 * PAD
-
-
-def _up(gpu, a):
-  return gpu.DeviceArray.from_host(a, dtype=a.dtype)
-
 
 def run_group(gpu, v, order, start, probs, k0, k1):
   """One launch into sentinel-filled outputs [nrec][nspec][ngroups]; returns (count, stat)."""
   from pymoc_amd import _lib
   nrec, nspec, n = v.shape
   ng, nq = len(start) - 1, len(probs)
-  series = _Padded(gpu, v)
+  series, v_ptr = _padded(gpu, v)
   start = np.ascontiguousarray(start, dtype=np.int32)
   probs = np.ascontiguousarray(probs, dtype=np.float64)
   d_order, d_start = _up(gpu, np.ascontiguousarray(order, dtype=np.int32)), _up(gpu, start)
@@ -58,7 +26,7 @@ def run_group(gpu, v, order, start, probs, k0, k1):
   stat = _up(gpu, np.full((nrec, nspec, ng, 5 + nq), V_SENTINEL))
   d = _lib.pm_series_group_stats()
   d.n, d.nspec, d.nrec, d.k0, d.k1, d.ngroups, d.nq = n, nspec, nrec, k0, k1, ng, nq
-  d.v, d.order, d.start, d.start_dev = series.ptr, d_order.ptr, start.ctypes.data, d_start.ptr
+  d.v, d.order, d.start, d.start_dev = v_ptr, d_order.ptr, start.ctypes.data, d_start.ptr
   d.q, d.q_dev = probs.ctypes.data, d_q.ptr
   _lib.check(_lib.lib.pm_series_group_stats(C.byref(d), count.ptr, stat.ptr, None))
   gpu.synchronize()
@@ -68,7 +36,7 @@ def run_group(gpu, v, order, start, probs, k0, k1):
 def run_member(gpu, v, lags, thr, dirs, k0, k1):
   from pymoc_amd import _lib
   nrec, nspec, n = v.shape
-  series = _Padded(gpu, v)
+  series, v_ptr = _padded(gpu, v)
   lags = np.ascontiguousarray(lags, dtype=np.int32)
   thr = np.ascontiguousarray(thr, dtype=np.float64)
   dirs = np.ascontiguousarray(dirs, dtype=np.int32)
@@ -78,7 +46,7 @@ def run_member(gpu, v, lags, thr, dirs, k0, k1):
   stat = _up(gpu, np.full((nspec, n, 6 + lags.size + 1), V_SENTINEL))  # (one double to spare)
   d = _lib.pm_series_member_stats()
   d.n, d.nspec, d.nrec, d.k0, d.k1, d.nlag = n, nspec, nrec, k0, k1, lags.size
-  d.v, d.lag, d.lag_dev = series.ptr, lags.ctypes.data, d_lag.ptr
+  d.v, d.lag, d.lag_dev = v_ptr, lags.ctypes.data, d_lag.ptr
   d.thr, d.thr_dev, d.dir, d.dir_dev = thr.ctypes.data, d_thr.ptr, dirs.ctypes.data, d_dir.ptr
   _lib.check(_lib.lib.pm_series_member_stats(C.byref(d), ints[0].ptr, ints[1].ptr, ints[2].ptr,
                                              stat.ptr, None))

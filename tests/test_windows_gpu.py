@@ -7,55 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from series_harness import I_SENTINEL, V_SENTINEL, _bits, _collect, _out, _padded, _up
 import windows_cases as WC
 
 pytestmark = pytest.mark.gpu
-
-V_SENTINEL, I_SENTINEL = -7.25, -77
-PAD = 97    # doubles on either side of the series inside its allocation
-SPARE = 33  # elements behind every output
-
-
-def _bits(got, want, what):
-  """Bit for bit, NaN <-> NaN (any payload), signed zeros as they are."""
-  got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-  assert got.shape == want.shape, (what, got.shape, want.shape)
-  gn, wn = np.isnan(got), np.isnan(want)
-  assert np.array_equal(gn, wn), (what, "NaN pattern", np.argwhere(gn != wn)[:5])
-  same = got.view(np.uint64) == want.view(np.uint64)
-  bad = np.argwhere(~(same | gn))
-  assert bad.size == 0, (what, bad[:5], got[tuple(bad[0])], want[tuple(bad[0])])
-
-
-def _up(gpu, a):
-  return gpu.DeviceArray.from_host(a, dtype=a.dtype)
-
-
-def _padded(gpu, v):
-  """The series inside a larger allocation whose padding alternates NaN with 7e30: a window with a
-  NaN is skipped by definition, so of a read outside the series it is the finite half that
-  shows."""
-  v = np.ascontiguousarray(v, dtype=np.float64)
-  buf = np.full(v.size + 2 * PAD, np.nan)
-  buf[0:PAD:2] = 7e30
-  buf[PAD + v.size::2] = 7e30
-  buf[PAD:PAD + v.size] = v.ravel()
-  return gpu.DeviceArray.from_host(buf)
-
-
-def _out(gpu, shape, dtype, sentinel):
-  size = int(np.prod(shape))
-  return _up(gpu, np.full(size + SPARE, sentinel, dtype=dtype)), size
-
-
-def _collect(out, shapes, what):
-  res = {}
-  for k, (dev, size) in out.items():
-    flat = dev.download().ravel()
-    assert (flat[size:] == shapes[k][2]).all(), (what, k, "behind the output")
-    res[k] = flat[:size].reshape(shapes[k][0])
-  return res
-
 
 def run(gpu, c, v=None, k0=None, k1=None):
   """One launch of the case's settings (on another series / record window if given) into
@@ -65,14 +20,14 @@ def run(gpu, c, v=None, k0=None, k1=None):
   k0, k1 = (c["k0"], c["k1"]) if k0 is None else (k0, k1)
   nrec, nspec, n = v.shape
   nwin = WC.nwin_of(k1 - k0, c["W"], c["S"])
-  series = _padded(gpu, v)
+  series, v_ptr = _padded(gpu, v)
   shapes = dict(out=((4, nwin, nspec, n), np.float64, V_SENTINEL),
                 nused=((nspec, n), np.int32, I_SENTINEL))
   out = {k: _out(gpu, *a) for k, a in shapes.items()}
   d = _lib.pm_series_windows()
   d.n, d.nspec, d.nrec, d.k0, d.k1 = n, nspec, nrec, k0, k1
   d.window, d.step, d.lag, d.detrend = c["W"], c["S"], c["Lg"], WC.DETRENDS.index(c["detrend"])
-  d.v, d.stt = series.ptr + 8 * PAD, WC.stt_of(c["W"])
+  d.v, d.stt = v_ptr, WC.stt_of(c["W"])
   _lib.check(_lib.lib.pm_series_windows(C.byref(d), out["out"][0].ptr, out["nused"][0].ptr, None))
   gpu.synchronize()
   return _collect(out, shapes, c["name"])
@@ -81,12 +36,12 @@ def run(gpu, c, v=None, k0=None, k1=None):
 def run_kendall(gpu, v, k0, k1):
   from pymoc_amd import _lib
   nrec, nspec, n = v.shape
-  series = _padded(gpu, v)
+  series, v_ptr = _padded(gpu, v)
   keys = ("conc", "disc", "tie", "nfin")
   shapes = {k: ((nspec, n), np.int32, I_SENTINEL) for k in keys}
   out = {k: _out(gpu, *a) for k, a in shapes.items()}
   d = _lib.pm_series_kendall()
-  d.n, d.nspec, d.nrec, d.k0, d.k1, d.v = n, nspec, nrec, k0, k1, series.ptr + 8 * PAD
+  d.n, d.nspec, d.nrec, d.k0, d.k1, d.v = n, nspec, nrec, k0, k1, v_ptr
   _lib.check(_lib.lib.pm_series_kendall(C.byref(d), *(out[k][0].ptr for k in keys), None))
   gpu.synchronize()
   res = _collect(out, shapes, "kendall")
