@@ -206,8 +206,15 @@ class ColumnEquiBatch(object):
       over = want & (t.m + nadd > self.max_nodes)  # _bvp.py: status 1, keep this solution
       self.status[over] = 1
       refine = want & ~over
-      if keep_mesh:
-        self.mesh = (t.m.copy(), t.x.copy(), ymesh.download(stream=self.stream))
+      if keep_mesh:  # a launch writes the rows of its active members only: keep the others' last
+        yh = ymesh.download(stream=self.stream)
+        ykeep = np.zeros_like(yh)
+        if self.mesh is not None:
+          ykeep[..., :self.mesh[2].shape[2]] = self.mesh[2]
+        ykeep[active != 0] = yh[active != 0]
+        past = np.arange(t.mmax) >= t.m[:, None, None]  # columns beyond a member's mesh
+        ykeep[np.broadcast_to(past, ykeep.shape)] = 0.
+        self.mesh = (t.m.copy(), t.x.copy(), ykeep)
       if not refine.any():
         break
       rms_h = rms.download(stream=self.stream)
