@@ -1409,6 +1409,71 @@ struct pm_series_kendall {
 int pm_series_kendall(const struct pm_series_kendall *d, int32_t *conc, int32_t *disc,
                       int32_t *tie, int32_t *nfin, pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Surrogate significance of the trends above (pymoc_amd.SeriesSurrogates,
+ * SeriesWindows.significance), on the device: ONE launch per entry and chunk of surrogates.  (no
+ * counterpart: what a user does with a random generator and a loop over the downloaded series.)
+ *
+ * pm_series_surrogates -- nb stationary AR(1) surrogates of every (index s, member m) series,
+ * written as a device series of K records in the layout above:
+ *   y[j][p][m],  j < K, p = i * nspec + s for surrogate b = b0 + i (i < nb, b0 the GLOBAL number of
+ *   the chunk's first surrogate), m < n -- a series of nb * nspec indices that pm_series_windows,
+ *   pm_series_kendall, pm_series_member_stats and pm_series_spectra read as it stands
+ * from the two fit values var[s][m] and ac[s][m]: planes out[2] and out[3] of pm_series_windows
+ * with ONE window spanning the record window (window = K, step = 1, lag = 1), hence
+ * K <= PM_SURROGATE_MAX = PM_WIN_MAX.  Per (b, s, m), every product and sum rounded on its own
+ * (-ffp-contract=off):
+ *   phi  = ac[s][m];  sd = sqrt(var[s][m]);  g = sd * sqrt(fmax(0.0, 1.0 - phi * phi))
+ *   xi_j = xi(seed, member0 + m, b, (s << 12) | j): the deviate of pm_forcing_noise above with the
+ *          Philox counter words { id_lo, id_hi, b, (s << 12) | j } -- the surrogate number takes
+ *          the slot `j` has there and (index, record) take the slot of `stream`; j < 4096 and
+ *          s <= 65535, so the packing is one to one.  (A NoiseForcing bound with the same seed uses
+ *          stream < PM_NOISE_STREAMS, that is s = 0 and j < 6 here: give the surrogates a seed of
+ *          their own where that matters.)
+ *   y_0  = sd * xi_0;   y_j = phi * y_{j-1} + g * xi_j
+ * sqrt and fmax are IEEE; only xi carries the tolerance stated above, so y equals the recurrence
+ * fed the deviates the device used (xi_out) bit for bit.  If phi or sd is not finite (a record
+ * window with a non-finite value, a constant series, var = inf) all K values of that series are
+ * NaN: stored, never skipped, so every entry above excludes and counts the series by its own rule.
+ * xi_out (may be NULL) has y's shape and holds the deviates used, of the NaN series too.  A
+ * surrogate depends on nothing but (seed, member0 + m, b, s, j) and its two fit values: not on n,
+ * on the shard, on the chunk [b0, b0 + nb) or on the launch geometry.
+ * Checked before the launch (PM_EINVAL, outputs untouched): no NULL pointer where one is read or
+ * written (xi_out may be NULL); n, nspec, nb >= 1; 1 <= K <= PM_SURROGATE_MAX; b0 >= 0 and
+ * b0 + nb <= 2^32; member0 >= 0; nb * nspec <= 65535 (the planes are the indices of the entries
+ * that read y); K * nb * nspec < 2^31; nb * nspec * n < 2^31.
+ *
+ * pm_series_exceed -- per (index s, member m), how many of nb surrogate trends reach the observed
+ * one.  From the counts of pm_series_kendall, observed [nspec][n] and surrogate [nb * nspec][n]
+ * (plane i * nspec + s), with
+ *   tau(c, d, t) = (double)(c - d) / sqrt((double)n0 * (double)(n0 - t)),  n0 = c + d + t
+ * (operands exact: counts below 2^23, the product below 2^46; sqrt and the division correctly
+ * rounded, so a NumPy restatement gives every tau bit for bit; NaN when n0 == t):
+ *   if tau_obs is NaN nothing is added; otherwise for each of the nb surrogates whose tau is not
+ *   NaN:  nvalid[s][m] += 1;  ge[s][m] += (tau_sur >= tau_obs);  le[s][m] += (tau_sur <= tau_obs)
+ * ge, le and nvalid (int32 [nspec][n]) are ADDED to: the caller zeroes them once and calls the
+ * entry once per chunk, on one stream; integer sums, so the chunking does not show.
+ * Checked before the launch (PM_EINVAL, outputs untouched): no NULL pointer; n, nspec, nb >= 1;
+ * nb * nspec <= 65535; nb * nspec * n < 2^31.                                                   */
+#define PM_SURROGATE_MAX 4096
+struct pm_series_surrogates {
+  int32_t n, nspec, K, nb;
+  int64_t b0;                            /* the GLOBAL number of the chunk's first surrogate      */
+  int64_t member0;                       /* the GLOBAL number of member 0                         */
+  uint64_t seed;
+  const double *var;                     /* device [nspec][n]                                     */
+  const double *ac;                      /* device [nspec][n]                                     */
+};
+int pm_series_surrogates(const struct pm_series_surrogates *d, double *y, double *xi_out,
+                         pm_stream_t stream);
+struct pm_series_exceed {
+  int32_t n, nspec, nb, reserved;
+  const int32_t *obs_conc, *obs_disc, *obs_tie;   /* device [nspec][n]                            */
+  const int32_t *sur_conc, *sur_disc, *sur_tie;   /* device [nb * nspec][n]                       */
+};
+int pm_series_exceed(const struct pm_series_exceed *d, int32_t *ge, int32_t *le, int32_t *nvalid,
+                     pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

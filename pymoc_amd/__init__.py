@@ -29,6 +29,7 @@ from .indices import RowIndices, IndexRecorder
 from .stats import SeriesStats
 from .spectra import SeriesSpectra
 from .windows import SeriesWindows
+from .surrogates import SeriesSurrogates
 from . import diagnostics
 from . import plotting
 from . import steady

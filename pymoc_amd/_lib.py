@@ -361,6 +361,23 @@ class pm_series_kendall(C.Structure):
               ("reserved3", C.c_int32), ("v", c_dp)]
 
 
+PM_SURROGATE_MAX = 4096
+
+
+class pm_series_surrogates(C.Structure):
+  """Mirror of `struct pm_series_surrogates` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("K", C.c_int32), ("nb", C.c_int32),
+              ("b0", C.c_int64), ("member0", C.c_int64), ("seed", C.c_uint64), ("var", c_dp),
+              ("ac", c_dp)]
+
+
+class pm_series_exceed(C.Structure):
+  """Mirror of `struct pm_series_exceed` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nb", C.c_int32), ("reserved", C.c_int32),
+              ("obs_conc", c_dp), ("obs_disc", c_dp), ("obs_tie", c_dp), ("sur_conc", c_dp),
+              ("sur_disc", c_dp), ("sur_tie", c_dp)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -479,6 +496,8 @@ SIGNATURES = {
                                              C.POINTER(C.c_int32)]),
     "pm_series_kendall": (C.c_int, [C.POINTER(pm_series_kendall), c_dp, c_dp, c_dp, c_dp,
                                     C.c_void_p]),
+    "pm_series_surrogates": (C.c_int, [C.POINTER(pm_series_surrogates), c_dp, c_dp, C.c_void_p]),
+    "pm_series_exceed": (C.c_int, [C.POINTER(pm_series_exceed), c_dp, c_dp, c_dp, C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -18,6 +18,7 @@
 // the buffer the launch does not read.
 #include <cmath>
 #include "common.hip.h"
+#include "philox.hip.h"  // philox_round, noise_deviate: the deviate of include/pymoc_hip.h
 
 namespace pm {
 
@@ -37,31 +38,6 @@ struct noise_args {
   noise_item item[PM_NOISE_MAX_TARGETS];
   uint32_t key0, key1, id_lo, id_hi, j;
 };
-
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-  const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-  c[0] = hi1 ^ c[1] ^ k0;
-  c[1] = lo1;
-  c[2] = hi0 ^ c[3] ^ k1;
-  c[3] = lo0;
-}
-
-// xi(seed, id, j, stream) of include/pymoc_hip.h
-__device__ __forceinline__ double noise_deviate(uint32_t key0, uint32_t key1, uint64_t id,
-                                                uint32_t j, uint32_t stream) {
-  uint32_t c[4] = {(uint32_t)id, (uint32_t)(id >> 32), j, stream};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, key0, key1);
-    key0 += 0x9E3779B9u;
-    key1 += 0xBB67AE85u;
-  }
-  const double d1 = ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6)) * 0x1p-53;
-  const double d2 = ((double)(c[2] >> 5) * 67108864.0 + (double)(c[3] >> 6)) * 0x1p-53;
-  const double R = sqrt(-2.0 * log(1.0 - d1));
-  return R * cos(6.283185307179586 * d2);
-}
 
 __global__ void __launch_bounds__(NOISE_BLOCK) k_forcing_noise(noise_args a) {
   noise_item it = a.item[0];

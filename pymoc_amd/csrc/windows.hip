@@ -294,7 +294,7 @@ int pm_series_windows(const struct pm_series_windows *dp, double *out, int32_t *
   PM_REQUIRE(d.detrend == PM_WIN_DETREND_NONE || d.detrend == PM_WIN_DETREND_CONSTANT ||
                  d.detrend == PM_WIN_DETREND_LINEAR,
              "unknown detrend %d", d.detrend);
-  const double stt = (double)W * ((double)W * (double)W - 1.0) / 12.0;  // an integer: exact
+  const double stt = (double)W * ((double)W * (double)W - 1.0) / 12.0;  // a multiple of a half: exact
   PM_REQUIRE(d.stt == stt, "stt %.17g is not W (W^2 - 1) / 12 = %.17g", d.stt, stt);
   const int nwin = (d.k1 - d.k0 - W) / d.step + 1;
   PM_REQUIRE((long long)nwin * d.nspec < (1ll << 30), "nwin * nspec = %lld is not below 2^30",

@@ -1,4 +1,5 @@
-"""Series: what SeriesStats, SeriesSpectra and SeriesWindows share -- the recorded series itself.
+"""Series: what SeriesStats, SeriesSpectra, SeriesWindows and SeriesSurrogates share -- the recorded
+series itself.
 
 A series is an `IndexRecorder`'s device layout v[record][index][member], float64 [nrec, nspec, n].
 This module is the one place that knows
@@ -52,7 +53,7 @@ class _Plane(object):
 
 class Series(object):
   """A checked source: `_rec` (the recorder or None), `_series`, `names`, `stream`, `nrec`, `nspec`,
-  `n`.  The base of the three Series* classes."""
+  `n`.  The base of the Series* classes."""
 
   def __init__(self, source, stream=None):
     self._rec = None

@@ -1,0 +1,228 @@
+"""SeriesSurrogates: stationary AR(1) surrogates of a recorded index series, generated on the
+device, and the counting behind `SeriesWindows.significance`.
+
+Kendall's tau of a sliding-window indicator means nothing by itself: overlapping windows make the
+indicator series strongly serially correlated, and stationary red noise routinely gives |tau| of
+0.5 and more.  The standard significance statement (Dakos et al. 2008, 2012; Boers 2021) is a
+surrogate test: fit a stationary null model to the detrended series, generate many surrogate
+series from it, run the identical window + Kendall pipeline on each, and report the fraction of
+surrogates whose tau reaches the observed one.  Here the null model is AR(1): the fit is
+pm_series_windows itself with ONE window spanning the record window (its `var` and lag-1 `ac` under
+the class's `detrend`), and pm_series_surrogates (csrc/surrogates.hip) writes the surrogates as a
+device series [K, nb * nspec, n] -- a source every `Series*` class accepts, so spectra or statistics
+of surrogates can be taken too.  The surrogate series never exist on the host.
+
+  fit(k0, k1)               the device `var` and `ac` [1, nspec, n] of the record window
+  generate(k0, k1, b0, nb)  (DeviceArray [K, nb * nspec, n], names): the surrogates b0 .. b0 + nb - 1
+                            of every series, named "%s#%d" % (name, b)
+
+A surrogate depends on nothing but (seed, global member, b, index, record) and the two fit values:
+not on n, the shard or the chunk [b0, b0 + nb) -- include/pymoc_hip.h states the definition,
+tests/surrogate_cases.py restates it.  A series whose fit is not finite (a record window with a
+non-finite value, a constant series) has NaN surrogates, which every later stage excludes and
+counts by its own rule.  The deviates come from the generator `NoiseForcing` uses; give the
+surrogates a seed of their own (the header says which coordinates would coincide).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, lib
+from .device import DeviceArray, _sh, launch_span
+from .series import Series, _Plane, as_int, by_name
+from .windows import _DETREND, SeriesWindows, launch_kendall, tau_b
+
+PLANES_MAX = 65535  # nb * nspec: the planes are the indices of the entries that read the series
+
+
+def as_seed(seed):
+  seed = as_int("seed", seed)
+  if not 0 <= seed < 1 << 64:
+    raise ValueError("seed must lie in [0, 2^64) (%d here)" % seed)
+  return seed
+
+
+def as_member0(member0, rec):
+  """`member0`, or for None the recorder's ensemble's first global member (0 without one)."""
+  if member0 is None:
+    return int(rec.ens._member0) if rec is not None else 0
+  member0 = as_int("member0", member0)
+  if member0 < 0:
+    raise ValueError("member0 must not be negative (%d here)" % member0)
+  return member0
+
+
+def launch_exceed(obs, sur, shape, acc, stream, timer):
+  """pm_series_exceed: the observed counts `obs` (conc, disc, tie [nspec, n]) against those of
+  shape = (nb, nspec, n) surrogates, `sur`, added into acc = (ge, le, nvalid); nothing
+  synchronised."""
+  d = _lib.pm_series_exceed()
+  d.nb, d.nspec, d.n = shape
+  d.obs_conc, d.obs_disc, d.obs_tie = (a.ptr for a in obs[:3])
+  d.sur_conc, d.sur_disc, d.sur_tie = (a.ptr for a in sur[:3])
+  with launch_span(timer, "k_series_exceed", stream):
+    check(lib.pm_series_exceed(C.byref(d), acc[0].ptr, acc[1].ptr, acc[2].ptr, _sh(stream)))
+
+
+class SeriesSurrogates(Series):
+  """`SeriesSurrogates(source, detrend="linear", seed=0, member0=None, stream=None)`.
+
+  source    an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
+  detrend   what the fit removes from the record window first: "linear", "constant" or "none"
+  seed      of the deviates, in [0, 2^64)
+  member0   the global number of member 0; None: the recorder's ensemble's (what its NoiseForcing
+            is bound with), 0 for a tuple source
+
+  A record window [k0, k1) holds K records, 4 <= K <= 4096."""
+
+  def __init__(self, source, detrend="linear", seed=0, member0=None, stream=None):
+    Series.__init__(self, source, stream)
+    if self.nspec > PLANES_MAX:
+      raise ValueError("nspec = %d is above %d" % (self.nspec, PLANES_MAX))
+    if detrend not in _DETREND:
+      raise ValueError("unknown detrend %r (one of linear, constant, none)" % (detrend,))
+    self.detrend, self.seed = detrend, as_seed(seed)
+    self.member0 = as_member0(member0, self._rec)
+
+  def _window(self, k0, k1):
+    k0, k1 = self._record_window(k0, k1)
+    K = k1 - k0
+    if not _lib.PM_WIN_MIN <= K <= _lib.PM_SURROGATE_MAX:
+      raise ValueError("window [%d, %d) holds %d records: the fit takes %d to %d"
+                       % (k0, k1, K, _lib.PM_WIN_MIN, _lib.PM_SURROGATE_MAX))
+    return k0, k1, K
+
+  def _chunk(self, b0, nb):
+    b0, nb = as_int("b0", b0), as_int("nb", nb)
+    if b0 < 0 or nb < 1 or b0 + nb > 1 << 32:
+      raise ValueError("surrogates [%d, %d) are not a range inside [0, 2^32)" % (b0, b0 + nb))
+    if nb * self.nspec > PLANES_MAX:
+      raise ValueError("nb * nspec = %d is above %d" % (nb * self.nspec, PLANES_MAX))
+    if nb * self.nspec * self.n >= 1 << 31:
+      raise ValueError("nb * nspec * n = %d is not below 2^31" % (nb * self.nspec * self.n))
+    return b0, nb
+
+  def names_of(self, b0, nb):
+    return ["%s#%d" % (nm, b) for b in range(b0, b0 + nb) for nm in self.names]
+
+  def fit(self, k0=0, k1=None, out=None):
+    """The null model of the record window: (var, ac), each a device series [1, nspec, n] -- one
+    launch of pm_series_windows with one window of K records, lag 1, nothing synchronised."""
+    k0, k1, K = self._window(k0, k1)
+    one = SeriesWindows((self._series, self.names), K, step=1, detrend=self.detrend, lag=1,
+                        stream=self.stream)
+    one._timer = self._timer  # (its launch span goes where this source's spans go)
+    out, _ = one._launch(k0, k1, 1, out=out)
+    shape = (1, self.nspec, self.n)
+    return _Plane(out, 2, shape), _Plane(out, 3, shape)
+
+  def _launch(self, fit, K, b0, nb, y, xi=None):
+    d = _lib.pm_series_surrogates()
+    d.n, d.nspec, d.K, d.nb, d.b0 = self.n, self.nspec, K, nb, b0
+    d.member0, d.seed, d.var, d.ac = self.member0, self.seed, fit[0].ptr, fit[1].ptr
+    with launch_span(self._timer(), "k_series_surrogates", self.stream):
+      check(lib.pm_series_surrogates(C.byref(d), y.ptr, None if xi is None else xi.ptr,
+                                     _sh(self.stream)))
+
+  def generate(self, k0=0, k1=None, b0=0, nb=1):
+    """The surrogates b0 .. b0 + nb - 1 of the record window [k0, k1): the fit, then one launch of
+    pm_series_surrogates.  Returns (DeviceArray [K, nb * nspec, n], names), a source of its own
+    (pass `stream=` this object's stream with it)."""
+    k0, k1, K = self._window(k0, k1)
+    b0, nb = self._chunk(b0, nb)
+    fit = self.fit(k0, k1)
+    y = DeviceArray((K, nb * self.nspec, self.n), np.float64)
+    self._launch(fit, K, b0, nb, y)
+    return y, self.names_of(b0, nb)
+
+
+class TrendSignificance(object):
+  """The surrogate test of one indicator's trend, each `[name] -> [n]`: the observed `tau`; among
+  the `nvalid` surrogates with a tau, `ge` have tau >= the observed one and `le` tau <= it;
+  `p_rising = (1 + ge) / (1 + nvalid)` and `p_falling = (1 + le) / (1 + nvalid)`, NaN where the
+  observed tau is NaN or nvalid is 0."""
+
+  def __init__(self, names, obs, ge, le, nvalid):
+    self.names = list(names)
+    tau = tau_b(*obs)
+    none = np.isnan(tau) | (nvalid == 0)
+    with np.errstate(all="ignore"):
+      p = [np.where(none, np.nan, (1.0 + c) / (1.0 + nvalid)) for c in (ge, le)]
+    self.tau, self.ge, self.le, self.nvalid, self.p_rising, self.p_falling = (
+        by_name(self.names, a) for a in (tau, ge, le, nvalid, p[0], p[1]))
+
+
+class Significance(object):
+  """What `SeriesWindows.significance` returns: `.var` and `.ac`, a `TrendSignificance` each, and
+  `nsur`."""
+
+  def __init__(self, var, ac, nsur):
+    self.var, self.ac, self.nsur = var, ac, nsur
+
+
+def chunk_size(nsur, max_bytes, K, nspec, n):
+  """The surrogates of one chunk: what max_bytes holds of 8 K nspec n bytes each, at most
+  65535 // nspec and nsur."""
+  nb = min(nsur, max_bytes // (8 * K * nspec * n), PLANES_MAX // nspec,
+           ((1 << 31) - 1) // (nspec * n))
+  if nb < 1:
+    raise ValueError("max_bytes = %d does not hold one surrogate of %d bytes (or nspec * n = %d "
+                     "is not below 2^31)" % (max_bytes, 8 * K * nspec * n, nspec * n))
+  return nb
+
+
+def significance(sw, k0, k1, nsur, seed, member0, max_bytes):
+  """`SeriesWindows.significance` (windows.py states what it does)."""
+  nsur, max_bytes = as_int("nsur", nsur), as_int("max_bytes", max_bytes)
+  seed, member0 = as_seed(seed), as_member0(member0, sw._rec)
+  k0, k1, nwin = sw._window(k0, k1)
+  K = k1 - k0
+  if nwin > _lib.PM_KENDALL_MAX:
+    raise ValueError("the record window [%d, %d) holds %d windows, more than %d"
+                     % (k0, k1, nwin, _lib.PM_KENDALL_MAX))
+  if K > _lib.PM_SURROGATE_MAX:
+    raise ValueError("the record window [%d, %d) holds %d records, more than %d"
+                     % (k0, k1, K, _lib.PM_SURROGATE_MAX))
+  if nsur < 1:
+    raise ValueError("nsur must be at least 1 (%d here)" % nsur)
+  nspec, n, stream, timer = sw.nspec, sw.n, sw.stream, sw._timer()
+  nbmax = chunk_size(nsur, max_bytes, K, nspec, n)
+  gen = SeriesSurrogates((sw._series, sw.names), detrend=sw.detrend, seed=seed, member0=member0,
+                         stream=stream)
+  gen._timer = sw._timer
+  # 1. the observed trends
+  out, _ = sw._launch(k0, k1, nwin)
+  shape = (nwin, nspec, n)
+  obs = [launch_kendall(_Plane(out, i, shape), shape, 0, nwin, stream, timer) for i in (2, 3)]
+  # 2. the fit and the zeroed accumulators
+  fit = gen.fit(k0, k1)
+  acc = [[DeviceArray.zeros((nspec, n), np.int32, stream=stream) for _ in range(3)]
+         for _ in range(2)]
+  # 3. chunk by chunk on the chunk's arrays, allocated once for the largest
+  y = DeviceArray((K, nbmax * nspec, n), np.float64)
+  wout = (DeviceArray((4, nwin, nbmax * nspec, n), np.float64),
+          DeviceArray((nbmax * nspec, n), np.int32))
+  cnt = [DeviceArray((nbmax * nspec, n), np.int32) for _ in range(4)]
+  subs = {}
+  for b0 in range(0, nsur, nbmax):
+    nb = min(nbmax, nsur - b0)
+    planes = nb * nspec
+    if nb not in subs:  # (at most two sizes: the chunks and the last one)
+      view = _Plane(y, 0, (K, planes, n))
+      subs[nb] = SeriesWindows((view, ["%d" % p for p in range(planes)]), sw.window, step=sw.step,
+                               detrend=sw.detrend, lag=sw.lag, stream=stream)
+      subs[nb]._timer = sw._timer
+    gen._launch(fit, K, b0, nb, y)
+    subs[nb]._launch(0, K, nwin, out=wout)
+    wshape = (nwin, planes, n)
+    for i, which in enumerate((2, 3)):
+      launch_kendall(_Plane(wout[0], which, wshape), wshape, 0, nwin, stream, timer, out=cnt)
+      launch_exceed(obs[i], cnt, (nb, nspec, n), acc[i], stream, timer)
+  # 4. the counts, and nothing else
+  res = []
+  for i in range(2):
+    o = [a.download(stream=stream) for a in obs[i][:3]]
+    ge, le, nvalid = (a.download(stream=stream) for a in acc[i])
+    res.append(TrendSignificance(sw.names, o, ge, le, nvalid))
+  return Significance(res[0], res[1], nsur)

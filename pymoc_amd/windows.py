@@ -17,6 +17,10 @@ number in one more (pm_series_kendall); only the results are downloaded.
                            device: tau, conc, disc, tie, nfin [name] -> [n]; only the counts are
                            downloaded
   kendall(source, k0, k1)  the same counts and tau of any device series
+  significance(k0, k1, nsur)
+                           the surrogate test of `trend`: AR(1) surrogates generated on the device
+                           (surrogates.py), each through the same two launches, and a counting
+                           launch; p_rising, p_falling and the three counts [name] -> [n]
 
 A window with a non-finite value is excluded and counted (`nused`), never propagated: its four
 indicators are NaN, which `across_members` and `trend` exclude and count in turn.  The definition
@@ -30,7 +34,8 @@ are: series.py.
 Out of scope:
   * Gaussian-kernel detrending;
   * skewness and higher moments;
-  * surrogate significance tests of tau;
+  * of the surrogate test: Fourier phase-randomised surrogates, ARMA orders above 1 (the null
+    model is AR(1)), and surrogates of `pos`;
   * anything across ranks: every rank treats its own members;
   * anything online: the indicators are computed from the recorded series, after the samples;
   * indicators of `pos` (the positions an IndexRecorder keeps next to the values);
@@ -52,9 +57,10 @@ INDICATORS = ("mean", "slope", "var", "ac")
 
 
 def stt_of(W):
-  """sum t_j^2 = W (W^2 - 1) / 12 of t_j = j - (W - 1) / 2: an integer below 2^53, exact."""
+  """sum t_j^2 = W (W^2 - 1) / 12 of t_j = j - (W - 1) / 2: a multiple of a half below 2^53 (a
+  whole number unless W = 2 mod 4), so exact -- the value the entry forms and checks."""
   W = int(W)
-  return float(W * (W * W - 1) // 12)
+  return float(W * (W * W - 1)) / 12.0
 
 
 def tau_b(conc, disc, tie):
@@ -237,4 +243,21 @@ class SeriesWindows(_Source):
       cnt = launch_kendall(_Plane(out, i, shape), shape, 0, nwin, self.stream, self._timer())
       res.append(Trend(self.names, *(a.download(stream=self.stream) for a in cnt)))
     return WindowTrend(*res)
+
+  def significance(self, k0=0, k1=None, nsur=1000, seed=0, member0=None, max_bytes=2 << 30):
+    """The surrogate test of `trend()`: `nsur` stationary AR(1) surrogates of every series, fitted
+    to the record window under this object's detrend (surrogates.py), each through the identical
+    window + Kendall pipeline, all on the device.  Returns a `surrogates.Significance`: `.var` and
+    `.ac`, each with tau (observed), ge, le, nvalid, p_rising = (1 + ge) / (1 + nvalid) and
+    p_falling = (1 + le) / (1 + nvalid) `[name] -> [n]`; p is NaN where the observed tau is NaN
+    or no surrogate has one.
+
+    The observed `trend` launches come first, then the fit; then, per chunk of
+    min(remaining, max_bytes // (8 K nspec n), 65535 // nspec) surrogates, pm_series_surrogates,
+    pm_series_windows, and pm_series_kendall + pm_series_exceed over the var and the ac planes, on
+    the chunk's device arrays, which every chunk reuses; nothing is synchronised inside the loop
+    and only the counts are downloaded.  The counts do not depend on the chunking.  `seed` and
+    `member0` as for `SeriesSurrogates`; K = k1 - k0 <= 4096."""
+    from .surrogates import significance  # (surrogates derives from this module)
+    return significance(self, k0, k1, nsur, seed, member0, max_bytes)
 
