@@ -1474,6 +1474,57 @@ struct pm_series_exceed {
 int pm_series_exceed(const struct pm_series_exceed *d, int32_t *ge, int32_t *le, int32_t *nvalid,
                      pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Kernel detrending of a recorded series (pymoc_amd.SeriesSmooth, SeriesWindows(detrend =
+ * "gaussian")), on the device: ONE launch.  (no counterpart: what a user computes with
+ * scipy.ndimage.gaussian_filter1d or R's ksmooth over the downloaded series.)  The series is
+ * v[k][s][m] as above, the record window [k0, k1), K = k1 - k0, 1 <= K <= PM_SMOOTH_MAX = 4096, and
+ * x_j = v[k0 + j][s][m], j < K.
+ * The caller passes a half-width H = half, 1 <= H <= PM_SMOOTH_HALF_MAX = 4095, and a weight table
+ * w[0 .. H] with w[0] == 1.0, every w[d] finite and > 0 and w[d + 1] <= w[d] (for a Gaussian of
+ * sigma records: w[d] = exp(-0.5 (d / sigma)^2)); the device evaluates no exp.  Per record j, with
+ *   lo = max(0, j - H),  hi = min(K - 1, j + H)
+ * every product and sum rounded on its own (-ffp-contract=off), both sums sequential in ascending
+ * i from +0.0 over the i in [lo, hi] with isfinite(x_i) only:
+ *   num     = sum w[|i - j|] * x_i
+ *   den     = sum w[|i - j|]
+ *   trend_j = num / den                       NaN when no record in reach is finite (0 / 0)
+ *   resid_j = x_j - trend_j if isfinite(x_j), else NaN
+ *   nbad[s][m] = the number of non-finite records of the record window
+ * A non-finite record is left out and counted, never propagated: the trend at such a record is the
+ * gap-filled value from its neighbours, its residual is NaN (pm_series_windows then excludes every
+ * window that holds it, by its own rule).  The edges are renormalised by den (Nadaraya-Watson, as
+ * R's ksmooth), not reflected: a record outside [k0, k1) is never read.
+ * Results, members contiguous in each:
+ *   trend[K][nspec][n], resid[K][nspec][n]   each a series of its own that every pm_series_* entry
+ *                                            reads as it stands; either may be NULL and is then not
+ *                                            stored
+ *   nbad[nspec][n]                           (int32)
+ * The result of a series depends on that member's values alone: not on the member's position in
+ * the batch, its neighbours, n or the launch geometry -- records are independent, so a block may
+ * take any range of them.  pm_series_smooth_geometry reports the tile of an H: the adjacent members
+ * and the consecutive records one block takes.
+ *
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): no NULL pointer where one is
+ * read or written (trend or resid may be NULL, not both); n, nspec, nrec >= 1; 0 <= k0 < k1 <= nrec;
+ * K <= PM_SMOOTH_MAX; H in [1, PM_SMOOTH_HALF_MAX]; the table conditions; nspec <= 65535; (member
+ * tiles) * (record chunks) < 2^31.  The checks read the HOST table w; the kernel reads the device
+ * copy of the same values.                                                                      */
+#define PM_SMOOTH_MAX 4096
+#define PM_SMOOTH_HALF_MAX 4095
+struct pm_series_smooth {
+  int32_t n, nspec, nrec, k0, k1, half, reserved1, reserved2;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  const double *w;                       /* HOST [half + 1]                                       */
+  const double *w_dev;                   /* DEVICE, the same values                               */
+};
+int pm_series_smooth(const struct pm_series_smooth *d, double *trend, double *resid, int32_t *nbad,
+                     pm_stream_t stream);
+int pm_series_smooth_geometry(int32_t half, int32_t *members, int32_t *records);
+/* The LDS bytes one block of a launch with this half-width over nrecords = K records asks for (all
+ * dynamic: the kernel has no static LDS); at most the 160 KiB of a CU for every valid (H, K).   */
+int pm_series_smooth_lds_bytes(int32_t half, int32_t nrecords, size_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ from .stats import SeriesStats
 from .spectra import SeriesSpectra
 from .windows import SeriesWindows
 from .surrogates import SeriesSurrogates
+from .smooth import SeriesSmooth
 from . import diagnostics
 from . import plotting
 from . import steady

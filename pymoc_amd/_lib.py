@@ -378,6 +378,16 @@ class pm_series_exceed(C.Structure):
               ("sur_disc", c_dp), ("sur_tie", c_dp)]
 
 
+PM_SMOOTH_MAX, PM_SMOOTH_HALF_MAX = 4096, 4095
+
+
+class pm_series_smooth(C.Structure):
+  """Mirror of `struct pm_series_smooth` (include/pymoc_hip.h); `w` is a HOST address."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("half", C.c_int32), ("reserved1", C.c_int32),
+              ("reserved2", C.c_int32), ("v", c_dp), ("w", C.c_void_p), ("w_dev", c_dp)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -498,6 +508,10 @@ SIGNATURES = {
                                     C.c_void_p]),
     "pm_series_surrogates": (C.c_int, [C.POINTER(pm_series_surrogates), c_dp, c_dp, C.c_void_p]),
     "pm_series_exceed": (C.c_int, [C.POINTER(pm_series_exceed), c_dp, c_dp, c_dp, C.c_void_p]),
+    "pm_series_smooth": (C.c_int, [C.POINTER(pm_series_smooth), c_dp, c_dp, c_dp, C.c_void_p]),
+    "pm_series_smooth_geometry": (C.c_int, [C.c_int32, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32)]),
+    "pm_series_smooth_lds_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

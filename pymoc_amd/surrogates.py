@@ -20,8 +20,11 @@ A surrogate depends on nothing but (seed, global member, b, index, record) and t
 not on n, the shard or the chunk [b0, b0 + nb) -- include/pymoc_hip.h states the definition,
 tests/surrogate_cases.py restates it.  A series whose fit is not finite (a record window with a
 non-finite value, a constant series) has NaN surrogates, which every later stage excludes and
-counts by its own rule.  The deviates come from the generator `NoiseForcing` uses; give the
-surrogates a seed of their own (the header says which coordinates would coincide).
+counts by its own rule.  Under detrend "gaussian" the fit is the smoother (smooth.py) followed by
+the one-window "constant" fit of its residual, and the surrogates are surrogates of that residual;
+`significance` then sends every chunk through the same smoother.  The deviates come from the
+generator `NoiseForcing` uses; give the surrogates a seed of their own (the header says which
+coordinates would coincide).
 """
 import ctypes as C
 
@@ -31,7 +34,8 @@ from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
 from .series import Series, _Plane, as_int, by_name
-from .windows import _DETREND, SeriesWindows, launch_kendall, tau_b
+from .smooth import SeriesSmooth
+from .windows import SeriesWindows, check_detrend, launch_kendall, residual_of, tau_b
 
 PLANES_MAX = 65535  # nb * nspec: the planes are the indices of the entries that read the series
 
@@ -66,22 +70,25 @@ def launch_exceed(obs, sur, shape, acc, stream, timer):
 
 
 class SeriesSurrogates(Series):
-  """`SeriesSurrogates(source, detrend="linear", seed=0, member0=None, stream=None)`.
+  """`SeriesSurrogates(source, detrend="linear", seed=0, member0=None, stream=None, sigma=None,
+  truncate=4.0)`.
 
   source    an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
-  detrend   what the fit removes from the record window first: "linear", "constant" or "none"
+  detrend   what the fit removes from the record window first: "linear", "constant", "none", or
+            "gaussian" (a Gaussian-kernel trend of `sigma` records, cut at `truncate` sigmas:
+            smooth.py; then the mean) -- the surrogates are then surrogates of the residual
   seed      of the deviates, in [0, 2^64)
   member0   the global number of member 0; None: the recorder's ensemble's (what its NoiseForcing
             is bound with), 0 for a tuple source
 
   A record window [k0, k1) holds K records, 4 <= K <= 4096."""
 
-  def __init__(self, source, detrend="linear", seed=0, member0=None, stream=None):
+  def __init__(self, source, detrend="linear", seed=0, member0=None, stream=None, sigma=None,
+               truncate=4.0):
     Series.__init__(self, source, stream)
     if self.nspec > PLANES_MAX:
       raise ValueError("nspec = %d is above %d" % (self.nspec, PLANES_MAX))
-    if detrend not in _DETREND:
-      raise ValueError("unknown detrend %r (one of linear, constant, none)" % (detrend,))
+    self._smooth, self._smoother = check_detrend(detrend, sigma, truncate), None
     self.detrend, self.seed = detrend, as_seed(seed)
     self.member0 = as_member0(member0, self._rec)
 
@@ -108,12 +115,18 @@ class SeriesSurrogates(Series):
 
   def fit(self, k0=0, k1=None, out=None):
     """The null model of the record window: (var, ac), each a device series [1, nspec, n] -- one
-    launch of pm_series_windows with one window of K records, lag 1, nothing synchronised."""
+    launch of pm_series_windows with one window of K records, lag 1, nothing synchronised.  Under
+    "gaussian" the smoother's launch first, then the "constant" fit of its residual."""
     k0, k1, K = self._window(k0, k1)
-    one = SeriesWindows((self._series, self.names), K, step=1, detrend=self.detrend, lag=1,
+    series, detrend = self._series, self.detrend
+    if self._smooth:
+      series, detrend = residual_of(self, self._smooth, k0, k1), "constant"
+      k0, k1 = 0, K
+    one = SeriesWindows((series, self.names), K, step=1, detrend=detrend, lag=1,
                         stream=self.stream)
     one._timer = self._timer  # (its launch span goes where this source's spans go)
     out, _ = one._launch(k0, k1, 1, out=out)
+    out._fitted = series  # (a residual lives as long as the fit read from it)
     shape = (1, self.nspec, self.n)
     return _Plane(out, 2, shape), _Plane(out, 3, shape)
 
@@ -161,14 +174,14 @@ class Significance(object):
     self.var, self.ac, self.nsur = var, ac, nsur
 
 
-def chunk_size(nsur, max_bytes, K, nspec, n):
-  """The surrogates of one chunk: what max_bytes holds of 8 K nspec n bytes each, at most
-  65535 // nspec and nsur."""
-  nb = min(nsur, max_bytes // (8 * K * nspec * n), PLANES_MAX // nspec,
+def chunk_size(nsur, max_bytes, K, nspec, n, per=8):
+  """The surrogates of one chunk: what max_bytes holds of per K nspec n bytes each (8; 16 under
+  "gaussian", the series plus its residual), at most 65535 // nspec and nsur."""
+  nb = min(nsur, max_bytes // (per * K * nspec * n), PLANES_MAX // nspec,
            ((1 << 31) - 1) // (nspec * n))
   if nb < 1:
     raise ValueError("max_bytes = %d does not hold one surrogate of %d bytes (or nspec * n = %d "
-                     "is not below 2^31)" % (max_bytes, 8 * K * nspec * n, nspec * n))
+                     "is not below 2^31)" % (max_bytes, per * K * nspec * n, nspec * n))
   return nb
 
 
@@ -187,20 +200,27 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes):
   if nsur < 1:
     raise ValueError("nsur must be at least 1 (%d here)" % nsur)
   nspec, n, stream, timer = sw.nspec, sw.n, sw.stream, sw._timer()
-  nbmax = chunk_size(nsur, max_bytes, K, nspec, n)
-  gen = SeriesSurrogates((sw._series, sw.names), detrend=sw.detrend, seed=seed, member0=member0,
-                         stream=stream)
+  gauss = sw._smooth
+  nbmax = chunk_size(nsur, max_bytes, K, nspec, n, per=16 if gauss else 8)
+  # 0. under "gaussian" everything below runs on the residual of the record window: records
+  #    [0, K) of a series of its own, with only the windows' means left to remove
+  obs_sw, r0, r1 = sw._detrended(k0, k1)
+  gen = SeriesSurrogates((obs_sw._series, sw.names), detrend=obs_sw.detrend, seed=seed,
+                         member0=member0, stream=stream)
   gen._timer = sw._timer
   # 1. the observed trends
-  out, _ = sw._launch(k0, k1, nwin)
+  out, _ = obs_sw._launch(r0, r1, nwin)
   shape = (nwin, nspec, n)
   obs = [launch_kendall(_Plane(out, i, shape), shape, 0, nwin, stream, timer) for i in (2, 3)]
   # 2. the fit and the zeroed accumulators
-  fit = gen.fit(k0, k1)
+  fit = gen.fit(r0, r1)
   acc = [[DeviceArray.zeros((nspec, n), np.int32, stream=stream) for _ in range(3)]
          for _ in range(2)]
   # 3. chunk by chunk on the chunk's arrays, allocated once for the largest
   y = DeviceArray((K, nbmax * nspec, n), np.float64)
+  yres = DeviceArray((K, nbmax * nspec, n), np.float64) if gauss else y
+  nbad = DeviceArray((nbmax * nspec, n), np.int32) if gauss else None
+  smooths = {}
   wout = (DeviceArray((4, nwin, nbmax * nspec, n), np.float64),
           DeviceArray((nbmax * nspec, n), np.int32))
   cnt = [DeviceArray((nbmax * nspec, n), np.int32) for _ in range(4)]
@@ -209,11 +229,18 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes):
     nb = min(nbmax, nsur - b0)
     planes = nb * nspec
     if nb not in subs:  # (at most two sizes: the chunks and the last one)
-      view = _Plane(y, 0, (K, planes, n))
-      subs[nb] = SeriesWindows((view, ["%d" % p for p in range(planes)]), sw.window, step=sw.step,
-                               detrend=sw.detrend, lag=sw.lag, stream=stream)
+      pnames = ["%d" % p for p in range(planes)]
+      view = _Plane(yres, 0, (K, planes, n))
+      subs[nb] = SeriesWindows((view, pnames), sw.window, step=sw.step, detrend=obs_sw.detrend,
+                               lag=sw.lag, stream=stream)
       subs[nb]._timer = sw._timer
+      if gauss:
+        smooths[nb] = SeriesSmooth((_Plane(y, 0, (K, planes, n)), pnames), gauss[0], gauss[1],
+                                   stream=stream)
+        smooths[nb]._timer = sw._timer
     gen._launch(fit, K, b0, nb, y)
+    if gauss:  # the same smoother the record went through
+      smooths[nb]._launch(0, K, resid=yres, nbad=nbad)
     subs[nb]._launch(0, K, nwin, out=wout)
     wshape = (nwin, planes, n)
     for i, which in enumerate((2, 3)):

@@ -31,8 +31,13 @@ correlation of the shifted pair (pandas.Series.autocorr).  An indicator is dated
 window (`record_end`), the early-warning convention.  What a source and a record window [k0, k1)
 are: series.py.
 
+`detrend="gaussian"` is the published estimator: a Gaussian-kernel trend is removed from the whole
+record window first (pm_series_smooth, smooth.py: one more launch, into a residual series of K
+records allocated per call), and the windows are cut from the residual with only their mean
+removed.  A record that is not finite has a NaN residual, so the windows that hold it are excluded
+as before.
+
 Out of scope:
-  * Gaussian-kernel detrending;
   * skewness and higher moments;
   * of the surrogate test: Fourier phase-randomised surrogates, ARMA orders above 1 (the null
     model is AR(1)), and surrogates of `pos`;
@@ -49,11 +54,39 @@ from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
 from .series import Series, _Plane, as_int, by_name
+from .smooth import SeriesSmooth, half_width
 from .stats import SeriesStats
 
 _DETREND = dict(linear=_lib.PM_WIN_DETREND_LINEAR, constant=_lib.PM_WIN_DETREND_CONSTANT,
                 none=_lib.PM_WIN_DETREND_NONE)
+GAUSSIAN = "gaussian"  # a detrend of the classes, not of the entry: the smoother, then "constant"
 INDICATORS = ("mean", "slope", "var", "ac")
+
+
+def check_detrend(detrend, sigma, truncate):
+  """A class's `detrend` with its `sigma` and `truncate`: (sigma, truncate, H) under "gaussian",
+  None under the in-window detrends, which take no sigma."""
+  if detrend != GAUSSIAN and detrend not in _DETREND:
+    raise ValueError("unknown detrend %r (one of linear, constant, none, gaussian)" % (detrend,))
+  if detrend != GAUSSIAN:
+    if sigma is not None:
+      raise ValueError("sigma is given (%r) but detrend is %r, not \"gaussian\"" % (sigma, detrend))
+    return None
+  if sigma is None:
+    raise ValueError("detrend \"gaussian\" needs sigma, the kernel's width in records")
+  return half_width(sigma, truncate)
+
+
+def residual_of(src, smooth, k0, k1):
+  """The smoother's launch over the records [k0, k1) of the checked source `src` with smooth =
+  (sigma, truncate, H): the residual as a device series [K, nspec, n], allocated here, nothing
+  synchronised; its launch span goes where the source's spans go."""
+  if src._smoother is None:  # (kept: the table is uploaded once per source object)
+    src._smoother = SeriesSmooth((src._series, src.names), smooth[0], smooth[1], stream=src.stream)
+    src._smoother._timer = src._timer
+  resid = src._smoother._alloc(k1 - k0)
+  src._smoother._launch(k0, k1, resid=resid)
+  return resid
 
 
 def stt_of(W):
@@ -139,20 +172,27 @@ class WindowTrend(object):
 
 
 class SeriesWindows(_Source):
-  """`SeriesWindows(source, window, step=1, detrend="linear", lag=1, groups=None, stream=None)`.
+  """`SeriesWindows(source, window, step=1, detrend="linear", lag=1, groups=None, stream=None,
+  sigma=None, truncate=4.0)`.
 
   source    an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
   window    W, the records of a window, in [4, 4096]; any integer
   step      S, the records between the starts of two consecutive windows, in [1, W]
-  detrend   "linear" (the window's least-squares line is removed), "constant" (its mean) or "none"
+  detrend   "linear" (the window's least-squares line is removed), "constant" (its mean), "none",
+            or "gaussian": a Gaussian-kernel trend is removed from the whole record window before
+            the windows are cut, then each window's mean
+  sigma     under "gaussian" (and only there): the kernel's standard deviation in records
+  truncate  its half-width in sigmas, in [1, 8] (smooth.py); K <= 4096 under "gaussian"
   lag       Lg of the autocorrelation, in [1, W - 2]
   groups    int array [n] of labels, for `across_members` (as SeriesStats)
 
   Each call of `compute` / `across_members` / `trend` is one launch of pm_series_windows on the
-  source's stream (and what follows it on the device).  [k0, k1) is a record window (series.py)
+  source's stream (and what follows it on the device), after one of pm_series_smooth under
+  "gaussian".  [k0, k1) is a record window (series.py)
   of at least W records."""
 
-  def __init__(self, source, window, step=1, detrend="linear", lag=1, groups=None, stream=None):
+  def __init__(self, source, window, step=1, detrend="linear", lag=1, groups=None, stream=None,
+               sigma=None, truncate=4.0):
     _Source.__init__(self, source, stream)
     W, S, Lg = as_int("window", window), as_int("step", step), as_int("lag", lag)
     if not _lib.PM_WIN_MIN <= W <= _lib.PM_WIN_MAX:
@@ -162,8 +202,7 @@ class SeriesWindows(_Source):
       raise ValueError("step must lie in [1, window = %d] (%d here)" % (W, S))
     if not 1 <= Lg <= W - 2:
       raise ValueError("lag must lie in [1, window - 2 = %d] (%d here)" % (W - 2, Lg))
-    if detrend not in _DETREND:
-      raise ValueError("unknown detrend %r (one of linear, constant, none)" % (detrend,))
+    self._smooth, self._smoother = check_detrend(detrend, sigma, truncate), None
     self.window, self.step, self.lag, self.detrend = W, S, Lg, detrend
     self.stt = stt_of(W)
     self._set_groups(groups)  # checked now, used by across_members
@@ -173,6 +212,9 @@ class SeriesWindows(_Source):
     if k1 - k0 < self.window:
       raise ValueError("window [%d, %d) holds %d records, fewer than the window length %d"
                        % (k0, k1, k1 - k0, self.window))
+    if self._smooth and k1 - k0 > _lib.PM_SMOOTH_MAX:
+      raise ValueError("window [%d, %d) holds %d records, more than the %d \"gaussian\" takes"
+                       % (k0, k1, k1 - k0, _lib.PM_SMOOTH_MAX))
     nwin = (k1 - k0 - self.window) // self.step + 1
     if nwin * self.nspec >= 1 << 30:
       raise ValueError("nwin * nspec = %d is not below 2^30" % (nwin * self.nspec))
@@ -192,6 +234,17 @@ class SeriesWindows(_Source):
     return (DeviceArray((4, nwin, self.nspec, self.n), np.float64),
             DeviceArray((self.nspec, self.n), np.int32))
 
+  def _detrended(self, k0, k1):
+    """(sw, k0, k1): what the window launch runs on.  This object and its record window; under
+    "gaussian" the smoother's launch, then a `SeriesWindows` with detrend "constant" over the
+    records [0, K) of the residual series."""
+    if not self._smooth:
+      return self, k0, k1
+    sub = SeriesWindows((residual_of(self, self._smooth, k0, k1), self.names), self.window,
+                        step=self.step, detrend="constant", lag=self.lag, stream=self.stream)
+    sub._timer = self._timer
+    return sub, 0, k1 - k0
+
   def _launch(self, k0, k1, nwin, out=None):
     """The launch alone: (out [4, nwin, nspec, n], nused [nspec, n]) on the device, nothing
     synchronised.  `out`: the arrays of an earlier call, written again."""
@@ -207,7 +260,8 @@ class SeriesWindows(_Source):
 
   def compute(self, k0=0, k1=None):
     k0, k1, nwin = self._window(k0, k1)
-    out, nused = self._launch(k0, k1, nwin)
+    sw, r0, r1 = self._detrended(k0, k1)
+    out, nused = sw._launch(r0, r1, nwin)
     return Windows(self.names, k0 + np.arange(nwin) * self.step + self.window - 1,
                    out.download(stream=self.stream), nused.download(stream=self.stream))
 
@@ -225,7 +279,8 @@ class SeriesWindows(_Source):
     st = SeriesStats((view, self.names), groups=self.groups, quantiles=quantiles,
                      stream=self.stream)
     self.group_labels = st.group_labels
-    self._launch(k0, k1, nwin, out=out)
+    sw, r0, r1 = self._detrended(k0, k1)
+    sw._launch(r0, r1, nwin, out=out)
     return st.across_members()
 
   def trend(self, k0=0, k1=None):
@@ -236,7 +291,8 @@ class SeriesWindows(_Source):
     if nwin > _lib.PM_KENDALL_MAX:
       raise ValueError("the record window [%d, %d) holds %d windows, more than %d"
                        % (k0, k1, nwin, _lib.PM_KENDALL_MAX))
-    out, _ = self._launch(k0, k1, nwin)
+    sw, r0, r1 = self._detrended(k0, k1)
+    out, _ = sw._launch(r0, r1, nwin)
     shape = (nwin, self.nspec, self.n)
     res = []
     for i in (2, 3):
@@ -257,7 +313,13 @@ class SeriesWindows(_Source):
     pm_series_windows, and pm_series_kendall + pm_series_exceed over the var and the ac planes, on
     the chunk's device arrays, which every chunk reuses; nothing is synchronised inside the loop
     and only the counts are downloaded.  The counts do not depend on the chunking.  `seed` and
-    `member0` as for `SeriesSurrogates`; K = k1 - k0 <= 4096."""
+    `member0` as for `SeriesSurrogates`; K = k1 - k0 <= 4096.
+
+    Under "gaussian" the pipeline applied to a surrogate is literally the one applied to the
+    record: the record window is smoothed once, the observed trends and the fit (one window,
+    "constant") come from its residual, the surrogates are AR(1) surrogates of the residual, and
+    every chunk goes through pm_series_smooth between pm_series_surrogates and pm_series_windows.
+    A surrogate then counts 16 K nspec n bytes against max_bytes, the series plus its residual."""
     from .surrogates import significance  # (surrogates derives from this module)
     return significance(self, k0, k1, nsur, seed, member0, max_bytes)
 
