@@ -12,7 +12,13 @@
 //  * ys(b): the reference root-finds bs(y) = b with scipy brentq (xtol 2e-12); bs(y) is an
 //    np.interp closure, i.e. piecewise linear, so the root is taken directly: first
 //    crossing north of argmin(bs), one linear solve.  Agrees with brentq to ~1e-15
-//    relative.  Members whose bs is NOT monotone north of its minimum have several
+//    relative.  A level that EQUALS a node value of bs north of the minimum and south of the last
+//    node is the exception: over a plateau of bs every point is a root and brentq ends where its
+//    iteration first meets f == 0 (kilometres from the plateau's southern end), and on a single
+//    node it ends within xtol of the node -- such a level runs brentq_interp, so it is the
+//    reference's bit for bit (b == min(bs) and b == bs[-1] are brentq's own two ends, returned
+//    before its first step: y[argmin] and y[-1]).  Per level, and no work for any other level.
+//    Members whose bs is NOT monotone north of its minimum have several
 //    crossings and the reference returns whichever one brentq's iteration lands on
 //    (examples/run_single_global_basin.py gets there): those members run brentq itself
 //    (brentq_interp below, SciPy's iteration step for step) and are flagged in `status`.
@@ -906,17 +912,24 @@ __device__ __forceinline__ void so_member(const pm_psi_so &a, int ops, int m_raw
       yv = yN;
     } else if (b[p] != b[p] || bs_nan) {
       yv = __builtin_nan("");
-    } else if (ambiguous) {  // several crossings: the one brentq's iteration finds
-      yv = brentq_interp(s_y, s_bs, ny, b[p], s_y[minind], yN);
     } else {
       // first crossing north of argmin: bs is non-decreasing there (not `ambiguous`), so the
       // first j with bs[j+1] >= b is a lower bound -- 6 probes instead of a walk over y
+      // (`ambiguous`: j = minind, unused)
       const int j = sj[p];
       const double f0 = s_bs[j], f1 = s_bs[j + 1];
-      if (f0 == b[p])
+      // b on a node value north of the minimum: bs may hold it over a plateau, where brentq ends
+      // wherever its iteration first meets f == 0, and on a single node it ends within its
+      // tolerance of the node, not on it -- such a level follows the iteration.  The two ends need
+      // none: f0 == b only at j = minind (brentq returns its lower end at once), and b == bs[-1]
+      // is met at y[-1] before the first step.
+      const bool on_node = f1 == b[p] && f0 != b[p] && j + 1 < ny - 1;
+      if (ambiguous || on_node)  // several crossings too: the one brentq's iteration finds
+        yv = brentq_interp(s_y, s_bs, ny, b[p], s_y[minind], yN);
+      else if (f0 == b[p])
         yv = s_y[j];
       else if (f1 == b[p])
-        yv = s_y[j + 1];
+        yv = yN;
       else
         yv = s_y[j] + (b[p] - f0) / ((f1 - f0) / (s_y[j + 1] - s_y[j]));
     }
