@@ -1525,6 +1525,100 @@ int pm_series_smooth_geometry(int32_t half, int32_t *members, int32_t *records);
  * dynamic: the kernel has no static LDS); at most the 160 KiB of a CU for every valid (H, K).   */
 int pm_series_smooth_lds_bytes(int32_t half, int32_t nrecords, size_t *bytes);
 
+/* ---------------------------------------------------------------------------------------------
+ * Abrupt shifts of a recorded series and per-member analysis ends (pymoc_amd.SeriesShifts,
+ * SeriesWindows.significance(until=)), on the device: ONE launch per entry.  (no counterpart: what
+ * a user does with a rolling two-window statistic and per-member slices of the downloaded series.)
+ * The series is v[k][s][m] as above, the record window [k0, k1), K = k1 - k0; records are numbered
+ * from k0 in everything below.  Every product and sum is rounded on its own (-ffp-contract=off);
+ * division and sqrt are IEEE.
+ *
+ * pm_series_shift_scan -- the largest shift between two adjacent windows of L = half records, from
+ * quantities pm_series_windows has already formed (so no sum gets a second order):
+ *   PM_WIN_MIN <= L <= PM_SHIFT_HALF_MAX = 2048;  2 L <= K
+ *   mean, var   the planes out[0] and out[2] of pm_series_windows over the same record window with
+ *               window = L, step = 1, PM_WIN_DETREND_CONSTANT, lag = 1: each [nwin][nspec][n],
+ *               nwin = K - L + 1, window i covering the records [i, i + L)
+ * Per (index s, member m) and candidate c = L .. K - L:
+ *   jump   = mean[c] - mean[c - L]
+ *   pooled = 0.5 * (var[c - L] + var[c])
+ *   stat   = jump / sqrt(pooled)           pooled == 0: +-inf, NaN when jump == 0 too
+ *   score  = -stat (dir[s] = -1: drops), fabs(stat) (dir[s] = 0), stat (dir[s] = +1: rises)
+ * A candidate COUNTS iff mean[c - L] and mean[c] are not NaN and its score is not NaN (an infinite
+ * score counts).  Results, members contiguous in each:
+ *   at[s][m]      (int32) the counting candidate with the largest score, the smallest c among equal
+ *                 scores (-0.0 == +0.0); -1 if none counts
+ *   first[s][m]   (int32) the smallest counting c with score >= thr[s]; -1 if there is none or
+ *                 thr[s] is NaN (no threshold)
+ *   ncand[s][m]   (int32) the number of counting candidates
+ *   val[4][nspec][n]   stat, jump, mean[c - L] and mean[c] at c = at; all four NaN when at = -1
+ * The selection does not depend on the order the candidates are visited in, and a series' result
+ * depends on that member's values alone: not on n, the shard or the launch geometry.
+ * Checked before the launch (PM_EINVAL, outputs untouched): no NULL pointer; n, nspec, nrec >= 1;
+ * 0 <= k0 < k1 <= nrec; L and K in the ranges above; nspec <= 65535; nwin * nspec < 2^30; every
+ * dir in {-1, 0, +1}; no thr infinite.  The checks read the HOST mirrors (thr, dir); the kernel
+ * reads the device copies of the same values.
+ *
+ * pm_series_censor -- a copy of a series with NaN from a per-member end on:
+ *   y[j][p][m] = (j < end) ? x[j][p][m] : NaN,   j < K, p = i * nspec + s, i < nb, m < n
+ *   w   = where[src[s]][m]
+ *   end = w < 0 ? K : max(0, w - guard)
+ * x and y are series of K records and nb * nspec indices (nb = 1: a record window of a recorded
+ * series, passed by the address of its first record; nb > 1: the planes of pm_series_surrogates).
+ * `where` (int32 [nspec][n], device) is `at` or `first` of the scan; src[s] names the index whose
+ * shift governs index s (the identity: every index by its own).  Kept records are copied as bits
+ * (a NaN keeps its payload); the NaN stored is the quiet NaN 0x7ff8000000000000.  y == x, in place,
+ * is allowed; any other overlap is not.  end_out (int32 [nspec][n], may be NULL) receives end,
+ * written once, not per plane.  Every pm_series_* entry excludes and counts the censored records
+ * by its own rule; for pm_series_smooth that is an edge renormalised at `end`.
+ * Checked before the launch (PM_EINVAL, outputs untouched): no NULL pointer where one is read or
+ * written (end_out may be NULL); n, nspec, nb, K >= 1; guard >= 0; every src in [0, nspec);
+ * nb * nspec <= 65535; K * nb * nspec < 2^31; nb * nspec * n < 2^31.  The check reads the HOST
+ * mirror of src; the kernel reads the device copy.
+ *
+ * pm_series_fit_ranged -- the null-model fit of every member up to its own end.  Per (index s,
+ * member m) with e = end[s][m]: var[s][m] and ac[s][m] are exactly what pm_series_windows defines
+ * for ONE window over the records [k0, k0 + e) -- W = e, lag 1, the same two passes in the same
+ * order, under detrend PM_WIN_DETREND_NONE, _CONSTANT or _LINEAR -- so they equal planes out[2] and
+ * out[3] of that launch bit for bit.  stt of every W is read from the table stt_tab[0 .. K],
+ * stt_tab[W] = W (W^2 - 1) / 12 (entries below PM_WIN_MIN are not read), which the entry checks
+ * against its own evaluation.  e < PM_WIN_MIN, e > K, or a non-finite record inside the range
+ * stores NaN in both values.  K <= PM_WIN_MAX.  var and ac are device [nspec][n], the shape
+ * pm_series_surrogates reads.  A series' result depends on that member's values and end alone.
+ * Checked before the launch (PM_EINVAL, outputs untouched): no NULL pointer; n, nspec, nrec >= 1;
+ * 0 <= k0 < k1 <= nrec; K <= PM_WIN_MAX; a known detrend; nspec * n < 2^31; the table.  The check
+ * reads the HOST table; the kernel reads the device copy of the same values.                   */
+#define PM_SHIFT_HALF_MAX 2048
+struct pm_series_shift_scan {
+  int32_t n, nspec, nrec, k0, k1, half, reserved1, reserved2;
+  const double *mean;                    /* device [k1 - k0 - half + 1][nspec][n]                 */
+  const double *var;                     /* device, the same shape                                */
+  const double *thr;                     /* HOST [nspec]; NaN: no threshold                       */
+  const double *thr_dev;                 /* DEVICE, the same values                               */
+  const int32_t *dir;                    /* HOST [nspec]: -1 drops, 0 either, +1 rises            */
+  const int32_t *dir_dev;                /* DEVICE, the same values                               */
+};
+int pm_series_shift_scan(const struct pm_series_shift_scan *d, int32_t *at, int32_t *first,
+                         int32_t *ncand, double *val, pm_stream_t stream);
+struct pm_series_censor {
+  int32_t n, nspec, K, nb, guard, reserved;
+  const double *x;                       /* device [K][nb * nspec][n]                             */
+  const int32_t *where;                  /* device [nspec][n]                                     */
+  const int32_t *src;                    /* HOST [nspec]                                          */
+  const int32_t *src_dev;                /* DEVICE, the same values                               */
+};
+int pm_series_censor(const struct pm_series_censor *d, double *y, int32_t *end_out,
+                     pm_stream_t stream);
+struct pm_series_fit_ranged {
+  int32_t n, nspec, nrec, k0, k1, detrend, reserved1, reserved2;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  const int32_t *end;                    /* device [nspec][n]                                     */
+  const double *stt_tab;                 /* HOST [k1 - k0 + 1]                                    */
+  const double *stt_tab_dev;             /* DEVICE, the same values                               */
+};
+int pm_series_fit_ranged(const struct pm_series_fit_ranged *d, double *var, double *ac,
+                         pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

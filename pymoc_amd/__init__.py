@@ -31,6 +31,7 @@ from .spectra import SeriesSpectra
 from .windows import SeriesWindows
 from .surrogates import SeriesSurrogates
 from .smooth import SeriesSmooth
+from .shifts import SeriesShifts
 from . import diagnostics
 from . import plotting
 from . import steady

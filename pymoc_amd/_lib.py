@@ -388,6 +388,33 @@ class pm_series_smooth(C.Structure):
               ("reserved2", C.c_int32), ("v", c_dp), ("w", C.c_void_p), ("w_dev", c_dp)]
 
 
+PM_SHIFT_HALF_MAX = 2048
+
+
+class pm_series_shift_scan(C.Structure):
+  """Mirror of `struct pm_series_shift_scan` (include/pymoc_hip.h); `thr` and `dir` are HOST
+  addresses."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("half", C.c_int32), ("reserved1", C.c_int32),
+              ("reserved2", C.c_int32), ("mean", c_dp), ("var", c_dp), ("thr", C.c_void_p),
+              ("thr_dev", c_dp), ("dir", C.c_void_p), ("dir_dev", c_dp)]
+
+
+class pm_series_censor(C.Structure):
+  """Mirror of `struct pm_series_censor` (include/pymoc_hip.h); `src` is a HOST address."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("K", C.c_int32), ("nb", C.c_int32),
+              ("guard", C.c_int32), ("reserved", C.c_int32), ("x", c_dp), ("where", c_dp),
+              ("src", C.c_void_p), ("src_dev", c_dp)]
+
+
+class pm_series_fit_ranged(C.Structure):
+  """Mirror of `struct pm_series_fit_ranged` (include/pymoc_hip.h); `stt_tab` is a HOST address."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("detrend", C.c_int32), ("reserved1", C.c_int32),
+              ("reserved2", C.c_int32), ("v", c_dp), ("end", c_dp), ("stt_tab", C.c_void_p),
+              ("stt_tab_dev", c_dp)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -512,6 +539,10 @@ SIGNATURES = {
     "pm_series_smooth_geometry": (C.c_int, [C.c_int32, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32)]),
     "pm_series_smooth_lds_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "pm_series_shift_scan": (C.c_int, [C.POINTER(pm_series_shift_scan), c_dp, c_dp, c_dp, c_dp,
+                                       C.c_void_p]),
+    "pm_series_censor": (C.c_int, [C.POINTER(pm_series_censor), c_dp, c_dp, C.c_void_p]),
+    "pm_series_fit_ranged": (C.c_int, [C.POINTER(pm_series_fit_ranged), c_dp, c_dp, C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -22,7 +22,9 @@ tests/surrogate_cases.py restates it.  A series whose fit is not finite (a recor
 non-finite value, a constant series) has NaN surrogates, which every later stage excludes and
 counts by its own rule.  Under detrend "gaussian" the fit is the smoother (smooth.py) followed by
 the one-window "constant" fit of its residual, and the surrogates are surrogates of that residual;
-`significance` then sends every chunk through the same smoother.  The deviates come from the
+`significance` then sends every chunk through the same smoother.  With `until=` (shifts.py) the
+test runs up to every member's own end: the record window censored, the fit per member over its
+own records (pm_series_fit_ranged), every chunk censored in place.  The deviates come from the
 generator `NoiseForcing` uses; give the surrogates a seed of their own (the header says which
 coordinates would coincide).
 """
@@ -34,6 +36,7 @@ from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
 from .series import Series, _Plane, as_int, by_name
+from .shifts import launch_fit_ranged
 from .smooth import SeriesSmooth
 from .windows import SeriesWindows, check_detrend, launch_kendall, residual_of, tau_b
 
@@ -185,7 +188,21 @@ def chunk_size(nsur, max_bytes, K, nspec, n, per=8):
   return nb
 
 
-def significance(sw, k0, k1, nsur, seed, member0, max_bytes):
+def censored_windows(sw, until, k0, k1):
+  """`sw` over the record window censored by `until` (shifts.py): pm_series_censor into a series of
+  K records of its own, and a `SeriesWindows` with sw's settings on it -- records [0, K)."""
+  K = k1 - k0
+  cens = DeviceArray((K, sw.nspec, sw.n), np.float64)
+  until._censor(sw._series.ptr + 8 * k0 * sw.nspec * sw.n, K, 1, cens.ptr, sw.stream,
+                sw._timer())
+  kw = dict(sigma=sw._smooth[0], truncate=sw._smooth[1]) if sw._smooth else {}
+  base = SeriesWindows((cens, sw.names), sw.window, step=sw.step, detrend=sw.detrend, lag=sw.lag,
+                       stream=sw.stream, **kw)
+  base._timer = sw._timer
+  return base
+
+
+def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None):
   """`SeriesWindows.significance` (windows.py states what it does)."""
   nsur, max_bytes = as_int("nsur", nsur), as_int("max_bytes", max_bytes)
   seed, member0 = as_seed(seed), as_member0(member0, sw._rec)
@@ -201,9 +218,13 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes):
     raise ValueError("nsur must be at least 1 (%d here)" % nsur)
   nspec, n, stream, timer = sw.nspec, sw.n, sw.stream, sw._timer()
   gauss = sw._smooth
+  if until is not None:  # the same test of the censored record window, a series of its own
+    until._until(sw, k0, k1)
   nbmax = chunk_size(nsur, max_bytes, K, nspec, n, per=16 if gauss else 8)
   # 0. under "gaussian" everything below runs on the residual of the record window: records
   #    [0, K) of a series of its own, with only the windows' means left to remove
+  if until is not None:
+    sw, k0, k1 = censored_windows(sw, until, k0, k1), 0, K
   obs_sw, r0, r1 = sw._detrended(k0, k1)
   gen = SeriesSurrogates((obs_sw._series, sw.names), detrend=obs_sw.detrend, seed=seed,
                          member0=member0, stream=stream)
@@ -213,7 +234,11 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes):
   shape = (nwin, nspec, n)
   obs = [launch_kendall(_Plane(out, i, shape), shape, 0, nwin, stream, timer) for i in (2, 3)]
   # 2. the fit and the zeroed accumulators
-  fit = gen.fit(r0, r1)
+  if until is None:
+    fit = gen.fit(r0, r1)
+  else:  # per member, over its records before its end
+    fit = launch_fit_ranged(obs_sw._series, (obs_sw.nrec, nspec, n), r0, r1, obs_sw.detrend,
+                            until.end, stream, timer)
   acc = [[DeviceArray.zeros((nspec, n), np.int32, stream=stream) for _ in range(3)]
          for _ in range(2)]
   # 3. chunk by chunk on the chunk's arrays, allocated once for the largest
@@ -239,6 +264,8 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes):
                                    stream=stream)
         smooths[nb]._timer = sw._timer
     gen._launch(fit, K, b0, nb, y)
+    if until is not None:  # cut where the record is
+      until._censor(y.ptr, K, nb, y.ptr, stream, timer)
     if gauss:  # the same smoother the record went through
       smooths[nb]._launch(0, K, resid=yres, nbad=nbad)
     subs[nb]._launch(0, K, nwin, out=wout)

@@ -20,7 +20,8 @@ number in one more (pm_series_kendall); only the results are downloaded.
   significance(k0, k1, nsur)
                            the surrogate test of `trend`: AR(1) surrogates generated on the device
                            (surrogates.py), each through the same two launches, and a counting
-                           launch; p_rising, p_falling and the three counts [name] -> [n]
+                           launch; p_rising, p_falling and the three counts [name] -> [n];
+                           `until=`: up to every member's own end (shifts.py)
 
 A window with a non-finite value is excluded and counted (`nused`), never propagated: its four
 indicators are NaN, which `across_members` and `trend` exclude and count in turn.  The definition
@@ -300,7 +301,8 @@ class SeriesWindows(_Source):
       res.append(Trend(self.names, *(a.download(stream=self.stream) for a in cnt)))
     return WindowTrend(*res)
 
-  def significance(self, k0=0, k1=None, nsur=1000, seed=0, member0=None, max_bytes=2 << 30):
+  def significance(self, k0=0, k1=None, nsur=1000, seed=0, member0=None, max_bytes=2 << 30,
+                   until=None):
     """The surrogate test of `trend()`: `nsur` stationary AR(1) surrogates of every series, fitted
     to the record window under this object's detrend (surrogates.py), each through the identical
     window + Kendall pipeline, all on the device.  Returns a `surrogates.Significance`: `.var` and
@@ -319,7 +321,15 @@ class SeriesWindows(_Source):
     record: the record window is smoothed once, the observed trends and the fit (one window,
     "constant") come from its residual, the surrogates are AR(1) surrogates of the residual, and
     every chunk goes through pm_series_smooth between pm_series_surrogates and pm_series_windows.
-    A surrogate then counts 16 K nspec n bytes against max_bytes, the series plus its residual."""
+    A surrogate then counts 16 K nspec n bytes against max_bytes, the series plus its residual.
+
+    `until`: a `SeriesShifts` (shifts.py) on which `detect()` and `censored()` have been called
+    over the same record window -- the test of every member up to its own end.  The observed series
+    is then the censored one (pm_series_censor; under "gaussian" smoothed afterwards), the fit is
+    pm_series_fit_ranged over every member's records [k0, k0 + end) (of the censored series, or of
+    its residual with "constant"), and every chunk goes through pm_series_censor in place, with
+    the same ends, between pm_series_surrogates and what follows: a surrogate is cut where the
+    record is.  Without `until` the launches are the ones listed above."""
     from .surrogates import significance  # (surrogates derives from this module)
-    return significance(self, k0, k1, nsur, seed, member0, max_bytes)
+    return significance(self, k0, k1, nsur, seed, member0, max_bytes, until)
 
