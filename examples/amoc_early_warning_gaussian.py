@@ -40,7 +40,9 @@ sys.path.insert(1, os.path.join(ROOT, "tests"))  # smooth_cases: the restatement
 sys.path.insert(2, os.path.join(ROOT, "examples"))  # amoc_early_warning: the experiment
 import pymoc_amd
 from pymoc_amd.device import DeviceArray, LaunchTimer, synchronize
+from pymoc_amd.series import Ctx
 from pymoc_amd.steady import YEAR
+from pymoc_amd.windows import launch_windows
 import amoc_early_warning as EW
 import smooth_cases as SC
 
@@ -152,12 +154,10 @@ def time_it(args):
     out = sw._alloc(nwin)
     # the launches compute() issues, into preallocated arrays: no allocation inside the span
     # (compute() itself allocates its residual and its outputs per call: that is in its wall time)
-    on_resid = pymoc_amd.SeriesWindows((resid, names), W, step=S, detrend="constant")
-
     def launches():
       if det == "gaussian":
         sm._launch(0, nrec, resid=resid, nbad=nbad)
-        on_resid._launch(0, nrec, nwin, out=out)
+        launch_windows(resid, 0, nrec, sw._par, Ctx(None, None), out=out)
       else:
         sw._launch(0, nrec, nwin, out=out)
     launches()

@@ -33,10 +33,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(1, os.path.join(ROOT, "tests"))  # windows_cases: the restatement, for the host route
 import pymoc_amd
 from pymoc_amd.device import DeviceArray, LaunchTimer, synchronize
-from pymoc_amd.series import _Plane
+from pymoc_amd.series import Ctx, _Plane
 from pymoc_amd.steady import YEAR
 from pymoc_amd.surrogates import SeriesSurrogates, chunk_size, launch_exceed
-from pymoc_amd.windows import launch_kendall
+from pymoc_amd.windows import launch_kendall, launch_windows
 from amoc_early_warning import _median_ms, ramp, sweep  # the same experiment
 import windows_cases as WC
 
@@ -111,9 +111,9 @@ def time_it(args):
   gen = SeriesSurrogates((dev, names), seed=args.surrogate_seed)
   fit = gen.fit()
   y = DeviceArray((K, planes, n), np.float64)
-  sub = pymoc_amd.SeriesWindows((y, ["%d" % p for p in range(planes)]), W, step=S)
+  ctx = Ctx(None, None)
   gen._launch(fit, K, 0, nb, y)  # warm-up
-  wout = sub._launch(0, K, nwin)
+  wout = launch_windows(y, 0, K, sw._par, ctx)
   wshape = (nwin, planes, n)
   cnt = launch_kendall(_Plane(wout[0], 3, wshape), wshape, 0, nwin, None, None)
   obs = launch_kendall(_Plane(sw._launch(0, K, nwin)[0], 3, (nwin, nspec, n)), (nwin, nspec, n), 0,
@@ -122,7 +122,7 @@ def time_it(args):
   synchronize()
   t = dict(
       gen=_median_ms(lambda: gen._launch(fit, K, 0, nb, y), args.reps) - null,
-      win=_median_ms(lambda: sub._launch(0, K, nwin, out=wout), args.reps) - null,
+      win=_median_ms(lambda: launch_windows(y, 0, K, sw._par, ctx, out=wout), args.reps) - null,
       kd=_median_ms(lambda: launch_kendall(_Plane(wout[0], 3, wshape), wshape, 0, nwin, None, None,
                                            out=cnt), args.reps) - null,
       ex=_median_ms(lambda: launch_exceed(obs, cnt, (nb, nspec, n), acc, None, None), args.reps) - null)
@@ -132,7 +132,7 @@ def time_it(args):
     print("  %-32s %10.1f us per chunk of %d surrogates" % (what + ":", 1e3 * t[key], nb))
   print("  one chunk, the six launches:     %10.1f us; the generator writes %.1f MB and the window "
         "launch reads them again" % (1e3 * chunk_ms, nb * v.nbytes / 1e6))
-  del sub, y, wout, cnt
+  del y, wout, cnt
   synchronize()
   t0 = time.perf_counter()
   sig = sw.significance(nsur=args.nsur, seed=args.surrogate_seed, max_bytes=args.max_bytes)

@@ -37,10 +37,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(1, os.path.join(ROOT, "tests"))  # shifts_cases, surrogate_cases: the restatements
 import pymoc_amd
 from pymoc_amd.device import DeviceArray, LaunchTimer, synchronize
-from pymoc_amd.series import _Plane
+from pymoc_amd.series import Ctx, _Plane
 from pymoc_amd.shifts import launch_fit_ranged, stt_table
 from pymoc_amd.steady import YEAR
 from pymoc_amd.surrogates import SeriesSurrogates
+from pymoc_amd.windows import launch_windows, win_par
 from amoc_early_warning import _median_ms, ramp, same_bits, sweep  # the same experiment
 import shifts_cases as SHC
 import surrogate_cases as SGC
@@ -177,14 +178,14 @@ def time_it(args):
         "a window scratch of %.1f MB; a drop detected in %.3f of the series; empty span %.1f us "
         "subtracted" % (n, nspec, K, v.nbytes / 1e6, L, K - 2 * L + 1, 32 * nwin * nspec * n / 1e6,
                         hit.mean(), 1e3 * null))
-  feed = pymoc_amd.SeriesWindows((dev, names), L, step=1, detrend="constant", lag=1)
-  out = feed._launch(0, K, nwin)
+  feed, ctx = win_par(L, 1, 1, "constant"), Ctx(None, None)
+  out = launch_windows(dev, 0, K, feed, ctx)
   scan_out = sh._scan(0, K, _Plane(out[0], 0, shape), _Plane(out[0], 2, shape))
   y, _ = sh.censored()
   fit = launch_fit_ranged(y, (K, nspec, n), 0, K, "linear", sh.end, None, None)
   synchronize()
   plane = 8 * nwin * nspec * n
-  t_win = _median_ms(lambda: feed._launch(0, K, nwin, out=out), args.reps) - null
+  t_win = _median_ms(lambda: launch_windows(dev, 0, K, feed, ctx, out=out), args.reps) - null
   t_scan = _median_ms(lambda: sh._scan(0, K, _Plane(out[0], 0, shape), _Plane(out[0], 2, shape),
                                        out=scan_out), args.reps) - null
   t_cens = _median_ms(lambda: sh._censor(dev.ptr, K, 1, y.ptr, None, None), args.reps) - null

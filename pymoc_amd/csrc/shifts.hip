@@ -161,14 +161,6 @@ __global__ __launch_bounds__(SH_BLOCK) void k_series_censor(
   for (int j = je; j < j1; ++j, o += t) y[o] = nan;
 }
 
-// The residual of the definition (windows.hip's, restated here: the units share no kernel code).
-template <int DET>
-__device__ __forceinline__ double fr_resid(double x, double mean, double slope, double t) {
-  if (DET == PM_WIN_DETREND_LINEAR) return (x - mean) - slope * t;
-  if (DET == PM_WIN_DETREND_CONSTANT) return x - mean;
-  return x;
-}
-
 template <int DET>
 __global__ __launch_bounds__(FR_BLOCK) void k_series_fit_ranged(
     const double *__restrict__ v, uint32_t plane, size_t rs, int k0, int K,
@@ -201,12 +193,12 @@ __global__ __launch_bounds__(FR_BLOCK) void k_series_fit_ranged(
       // pass 2: q = sum r_j r_j, c = sum_{j < W - 1} r_j r_{j + 1}
       double q = 0.0, c = 0.0;
       t = 0.0 - half;
-      double prev = fr_resid<DET>(xw[0], mean, slope, t);
+      double prev = series_resid<DET>(xw[0], mean, slope, t);
       q = q + prev * prev;
 #pragma unroll 4
       for (int j = 1; j < W; ++j) {
         t = t + 1.0;
-        const double r = fr_resid<DET>(xw[(size_t)j * rs], mean, slope, t);
+        const double r = series_resid<DET>(xw[(size_t)j * rs], mean, slope, t);
         c = c + prev * r;
         q = q + r * r;
         prev = r;
@@ -257,14 +249,10 @@ int pm_series_censor(const struct pm_series_censor *dp, double *y, int32_t *end_
                      pm_stream_t stream) {
   PM_REQUIRE(dp, "d is NULL");
   const struct pm_series_censor &d = *dp;
-  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nb >= 1, "n %d, nspec %d or nb %d < 1", d.n, d.nspec,
-             d.nb);
+  PM_PLANES_REQUIRE_DIMS(d);
   PM_REQUIRE(d.K >= 1, "K %d < 1", d.K);
   PM_REQUIRE(d.guard >= 0, "guard %d < 0", d.guard);
-  const long long planes = (long long)d.nb * d.nspec;
-  PM_REQUIRE(planes <= 65535, "nb * nspec = %lld > 65535", planes);
-  PM_REQUIRE(planes * d.K < (1ll << 31), "K * nb * nspec = %lld is not below 2^31", planes * d.K);
-  PM_REQUIRE(planes * d.n < (1ll << 31), "nb * nspec * n = %lld is not below 2^31", planes * d.n);
+  PM_PLANES_REQUIRE(d, d.K);
   PM_REQUIRE(d.x && d.where, "x or where is NULL");
   PM_REQUIRE(d.src && d.src_dev, "src (host or device) is NULL");
   PM_REQUIRE(y, "y is NULL");
@@ -293,38 +281,25 @@ int pm_series_fit_ranged(const struct pm_series_fit_ranged *dp, double *var, dou
   const int K = d.k1 - d.k0;
   PM_REQUIRE(K <= PM_WIN_MAX, "the window [%d, %d) holds %d records, more than %d", d.k0, d.k1, K,
              PM_WIN_MAX);
-  PM_REQUIRE(d.detrend == PM_WIN_DETREND_NONE || d.detrend == PM_WIN_DETREND_CONSTANT ||
-                 d.detrend == PM_WIN_DETREND_LINEAR,
-             "unknown detrend %d", d.detrend);
-  PM_REQUIRE((long long)d.nspec * d.n < (1ll << 31), "nspec * n = %lld is not below 2^31",
-             (long long)d.nspec * d.n);
-  PM_REQUIRE(d.v && d.end, "v or end is NULL");
-  PM_REQUIRE(d.stt_tab && d.stt_tab_dev, "stt_tab (host or device) is NULL");
-  PM_REQUIRE(var && ac, "var or ac is NULL");
-  for (int W = PM_WIN_MIN; W <= K; ++W) {
-    const double stt = (double)W * ((double)W * (double)W - 1.0) / 12.0;  // a multiple of a half: exact
-    PM_REQUIRE(d.stt_tab[W] == stt, "stt_tab[%d] = %.17g is not W (W^2 - 1) / 12 = %.17g", W,
-               d.stt_tab[W], stt);
-  }
-  hipStream_t st = resolve_stream(stream);
-  const uint32_t plane = (uint32_t)d.nspec * (uint32_t)d.n;
-  const size_t rs = (size_t)plane;
-  const dim3 grid((plane + FR_BLOCK - 1) / FR_BLOCK), block(FR_BLOCK);
-  switch (d.detrend) {
-    case PM_WIN_DETREND_LINEAR:
-      hipLaunchKernelGGL(k_series_fit_ranged<PM_WIN_DETREND_LINEAR>, grid, block, 0, st, d.v, plane,
-                         rs, (int)d.k0, K, d.end, d.stt_tab_dev, var, ac);
-      break;
-    case PM_WIN_DETREND_CONSTANT:
-      hipLaunchKernelGGL(k_series_fit_ranged<PM_WIN_DETREND_CONSTANT>, grid, block, 0, st, d.v,
-                         plane, rs, (int)d.k0, K, d.end, d.stt_tab_dev, var, ac);
-      break;
-    default:
-      hipLaunchKernelGGL(k_series_fit_ranged<PM_WIN_DETREND_NONE>, grid, block, 0, st, d.v, plane,
-                         rs, (int)d.k0, K, d.end, d.stt_tab_dev, var, ac);
-  }
-  PM_HIP(hipGetLastError());
-  return PM_OK;
+  return series_by_detrend(d.detrend, [&](auto det) -> int {
+    PM_REQUIRE((long long)d.nspec * d.n < (1ll << 31), "nspec * n = %lld is not below 2^31",
+               (long long)d.nspec * d.n);
+    PM_REQUIRE(d.v && d.end, "v or end is NULL");
+    PM_REQUIRE(d.stt_tab && d.stt_tab_dev, "stt_tab (host or device) is NULL");
+    PM_REQUIRE(var && ac, "var or ac is NULL");
+    for (int W = PM_WIN_MIN; W <= K; ++W)
+      PM_REQUIRE(d.stt_tab[W] == series_stt(W),
+                 "stt_tab[%d] = %.17g is not W (W^2 - 1) / 12 = %.17g", W, d.stt_tab[W],
+                 series_stt(W));
+    hipStream_t st = resolve_stream(stream);
+    const uint32_t plane = (uint32_t)d.nspec * (uint32_t)d.n;
+    const size_t rs = (size_t)plane;
+    hipLaunchKernelGGL(k_series_fit_ranged<decltype(det)::value>,
+                       dim3((plane + FR_BLOCK - 1) / FR_BLOCK), dim3(FR_BLOCK), 0, st, d.v, plane,
+                       rs, (int)d.k0, K, d.end, d.stt_tab_dev, var, ac);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+  });
 }
 
 }  // extern "C"

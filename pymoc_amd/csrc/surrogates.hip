@@ -99,17 +99,13 @@ int pm_series_surrogates(const struct pm_series_surrogates *dp, double *y, doubl
                          pm_stream_t stream) {
   PM_REQUIRE(dp, "d is NULL");
   const struct pm_series_surrogates &d = *dp;
-  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nb >= 1, "n %d, nspec %d or nb %d < 1", d.n, d.nspec,
-             d.nb);
+  PM_PLANES_REQUIRE_DIMS(d);
   PM_REQUIRE(d.K >= 1 && d.K <= PM_SURROGATE_MAX, "K %d outside [1, %d]", d.K, PM_SURROGATE_MAX);
   PM_REQUIRE(d.b0 >= 0 && d.b0 + (int64_t)d.nb <= (1ll << 32),
              "surrogates [%lld, %lld) are not inside [0, 2^32)", (long long)d.b0,
              (long long)d.b0 + d.nb);
   PM_REQUIRE(d.member0 >= 0, "member0 %lld < 0", (long long)d.member0);
-  const long long planes = (long long)d.nb * d.nspec;
-  PM_REQUIRE(planes <= 65535, "nb * nspec = %lld > 65535", planes);
-  PM_REQUIRE(planes * d.K < (1ll << 31), "K * nb * nspec = %lld is not below 2^31", planes * d.K);
-  PM_REQUIRE(planes * d.n < (1ll << 31), "nb * nspec * n = %lld is not below 2^31", planes * d.n);
+  PM_PLANES_REQUIRE(d, d.K);
   PM_REQUIRE(d.var && d.ac, "var or ac is NULL");
   PM_REQUIRE(y, "y is NULL");
   hipStream_t st = resolve_stream(stream);
@@ -134,11 +130,8 @@ int pm_series_exceed(const struct pm_series_exceed *dp, int32_t *ge, int32_t *le
                      pm_stream_t stream) {
   PM_REQUIRE(dp, "d is NULL");
   const struct pm_series_exceed &d = *dp;
-  PM_REQUIRE(d.n >= 1 && d.nspec >= 1 && d.nb >= 1, "n %d, nspec %d or nb %d < 1", d.n, d.nspec,
-             d.nb);
-  const long long planes = (long long)d.nb * d.nspec;
-  PM_REQUIRE(planes <= 65535, "nb * nspec = %lld > 65535", planes);
-  PM_REQUIRE(planes * d.n < (1ll << 31), "nb * nspec * n = %lld is not below 2^31", planes * d.n);
+  PM_PLANES_REQUIRE_DIMS(d);
+  PM_PLANES_REQUIRE(d, 1);  // (K = 1: the counts have no records)
   PM_REQUIRE(d.obs_conc && d.obs_disc && d.obs_tie, "an observed count array is NULL");
   PM_REQUIRE(d.sur_conc && d.sur_disc && d.sur_tie, "a surrogate count array is NULL");
   PM_REQUIRE(ge && le && nvalid, "ge, le or nvalid is NULL");

@@ -77,14 +77,6 @@ inline size_t wn_lds(const WnGeom &g, int span) {
   return sizeof(double) * (size_t)span * g.tm + sizeof(int) * g.tm;
 }
 
-// The residual of the definition.
-template <int DET>
-__device__ __forceinline__ double wn_resid(double x, double mean, double slope, double t) {
-  if (DET == PM_WIN_DETREND_LINEAR) return (x - mean) - slope * t;
-  if (DET == PM_WIN_DETREND_CONSTANT) return x - mean;
-  return x;
-}
-
 template <int DET, bool LAG1>
 __global__ __launch_bounds__(WN_THREADS) void k_series_windows(
     const double *__restrict__ v, int n, int nspec, int k0, int W, int S, int Lg, int nwin,
@@ -143,12 +135,12 @@ __global__ __launch_bounds__(WN_THREADS) void k_series_windows(
       double q = 0.0, c = 0.0;
       t = 0.0 - half;
       if (LAG1) {
-        double prev = wn_resid<DET>(xw[0], mean, slope, t);
+        double prev = series_resid<DET>(xw[0], mean, slope, t);
         q = q + prev * prev;
 #pragma unroll 4
         for (int j = 1; j < W; ++j) {
           t = t + 1.0;
-          const double r = wn_resid<DET>(xw[j << ltm], mean, slope, t);
+          const double r = series_resid<DET>(xw[j << ltm], mean, slope, t);
           c = c + prev * r;
           q = q + r * r;
           prev = r;
@@ -158,15 +150,15 @@ __global__ __launch_bounds__(WN_THREADS) void k_series_windows(
         const double dl = (double)Lg;
 #pragma unroll 2
         for (int j = 0; j < nl; ++j) {
-          const double r = wn_resid<DET>(xw[j << ltm], mean, slope, t);
-          const double r2 = wn_resid<DET>(xw[(j + Lg) << ltm], mean, slope, t + dl);
+          const double r = series_resid<DET>(xw[j << ltm], mean, slope, t);
+          const double r2 = series_resid<DET>(xw[(j + Lg) << ltm], mean, slope, t + dl);
           q = q + r * r;
           c = c + r * r2;
           t = t + 1.0;
         }
 #pragma unroll 2
         for (int j = nl; j < W; ++j) {
-          const double r = wn_resid<DET>(xw[j << ltm], mean, slope, t);
+          const double r = series_resid<DET>(xw[j << ltm], mean, slope, t);
           q = q + r * r;
           t = t + 1.0;
         }
@@ -291,30 +283,20 @@ int pm_series_windows(const struct pm_series_windows *dp, double *out, int32_t *
   PM_REQUIRE(d.lag >= 1 && d.lag <= W - 2, "lag %d outside [1, window - 2 = %d]", d.lag, W - 2);
   PM_REQUIRE(d.k1 - d.k0 >= W, "the record window [%d, %d) is shorter than the window length %d",
              d.k0, d.k1, W);
-  PM_REQUIRE(d.detrend == PM_WIN_DETREND_NONE || d.detrend == PM_WIN_DETREND_CONSTANT ||
-                 d.detrend == PM_WIN_DETREND_LINEAR,
-             "unknown detrend %d", d.detrend);
-  const double stt = (double)W * ((double)W * (double)W - 1.0) / 12.0;  // a multiple of a half: exact
-  PM_REQUIRE(d.stt == stt, "stt %.17g is not W (W^2 - 1) / 12 = %.17g", d.stt, stt);
-  const int nwin = (d.k1 - d.k0 - W) / d.step + 1;
-  PM_REQUIRE((long long)nwin * d.nspec < (1ll << 30), "nwin * nspec = %lld is not below 2^30",
-             (long long)nwin * d.nspec);
-  PM_REQUIRE(d.nspec <= 65535, "nspec = %d > 65535", d.nspec);
-  PM_REQUIRE(d.v, "v is NULL");
-  PM_REQUIRE(out && nused, "out or nused is NULL");
-  hipStream_t st = resolve_stream(stream);
-  const bool lag1 = d.lag == 1;
-  switch (d.detrend) {
-    case PM_WIN_DETREND_LINEAR:
-      return lag1 ? wn_launch<PM_WIN_DETREND_LINEAR, true>(d, nwin, st, out, nused)
-                  : wn_launch<PM_WIN_DETREND_LINEAR, false>(d, nwin, st, out, nused);
-    case PM_WIN_DETREND_CONSTANT:
-      return lag1 ? wn_launch<PM_WIN_DETREND_CONSTANT, true>(d, nwin, st, out, nused)
-                  : wn_launch<PM_WIN_DETREND_CONSTANT, false>(d, nwin, st, out, nused);
-    default:
-      return lag1 ? wn_launch<PM_WIN_DETREND_NONE, true>(d, nwin, st, out, nused)
-                  : wn_launch<PM_WIN_DETREND_NONE, false>(d, nwin, st, out, nused);
-  }
+  return series_by_detrend(d.detrend, [&](auto det) -> int {
+    PM_REQUIRE(d.stt == series_stt(W), "stt %.17g is not W (W^2 - 1) / 12 = %.17g", d.stt,
+               series_stt(W));
+    const int nwin = (d.k1 - d.k0 - W) / d.step + 1;
+    PM_REQUIRE((long long)nwin * d.nspec < (1ll << 30), "nwin * nspec = %lld is not below 2^30",
+               (long long)nwin * d.nspec);
+    PM_REQUIRE(d.nspec <= 65535, "nspec = %d > 65535", d.nspec);
+    PM_REQUIRE(d.v, "v is NULL");
+    PM_REQUIRE(out && nused, "out or nused is NULL");
+    hipStream_t st = resolve_stream(stream);
+    constexpr int DET = decltype(det)::value;
+    return d.lag == 1 ? wn_launch<DET, true>(d, nwin, st, out, nused)
+                      : wn_launch<DET, false>(d, nwin, st, out, nused);
+  });
 }
 
 int pm_series_kendall(const struct pm_series_kendall *dp, int32_t *conc, int32_t *disc,

@@ -1,5 +1,5 @@
-"""Series: what SeriesStats, SeriesSpectra, SeriesWindows and SeriesSurrogates share -- the recorded
-series itself.
+"""Series: what the Series* classes (stats, spectra, windows, smooth, surrogates, shifts) share --
+the recorded series itself.
 
 A series is an `IndexRecorder`'s device layout v[record][index][member], float64 [nrec, nspec, n].
 This module is the one place that knows
@@ -10,13 +10,18 @@ This module is the one place that knows
                      per index
   the record window  [k0, k1) inside the nrec records (k1 = None: nrec); with a recorder as source
                      a window that holds a record never written (`rec.steps == -1`) is a ValueError
-  a plane            `_Plane`: out[i] of a device array as a device series of its own
+  a device view      anything with `.ptr` and `.shape` = (nrec, nspec, n): a DeviceArray, a `View`
+                     (`records`: a record window of one), a `_Plane` (out[i] of a device array,
+                     with `keep`, what it was computed from and must outlive it)
+  the launch context `Ctx` = (stream, timer): where a launch function (launch_*: a view, plain
+                     parameters, a context) enqueues its kernel and records its span
   indexing by name   `by_name`: `result.mean[name]`, one dict for every result class
 
-and the small pieces around a launch: the timer, the lazy upload of host mirrors, the check of an
-integer argument and of group labels.  A limit one kernel has (nspec <= 65535, say) stays with its
-class.
+and the small pieces around a launch: the lazy upload of host mirrors, the check of an integer
+argument and of group labels.  A limit one kernel has (nspec <= 65535, say) stays with its class.
 """
+import collections
+
 import numpy as np
 
 from .device import DeviceArray
@@ -41,14 +46,25 @@ def by_name(names, arr):
   return _Named((nm, np.ascontiguousarray(arr[s])) for s, nm in enumerate(names))
 
 
+Ctx = collections.namedtuple("Ctx", "stream timer")
+View = collections.namedtuple("View", "ptr shape")
+
+
+def records(x, k0, k1):
+  """The records [k0, k1) of the device view `x` as a view of their own (x owns the memory)."""
+  return View(x.ptr + 8 * k0 * int(np.prod(x.shape[1:])), (k1 - k0,) + tuple(x.shape[1:]))
+
+
 class _Plane(object):
   """out[i] of a device array out[..][nrec][nspec][n] as a device series of its own, `shape` =
-  (nrec, nspec, n): an address, a shape and a dtype (the parent owns the memory and is kept
-  alive)."""
+  (nrec, nspec, n): an address, a shape and a dtype.  The parent owns the memory and is kept
+  alive, and so is `keep`: the device arrays the plane was computed from by a launch that may not
+  have run yet."""
 
-  def __init__(self, parent, i, shape):
+  def __init__(self, parent, i, shape, keep=()):
     self._parent, self.shape, self.dtype = parent, tuple(shape), np.dtype(np.float64)
     self.ptr = parent.ptr + 8 * i * int(np.prod(shape))
+    self.keep = tuple(keep)
 
 
 class Series(object):
@@ -99,6 +115,9 @@ class Series(object):
 
   def _timer(self):
     return self._rec.ens.timer if self._rec is not None else None
+
+  def _ctx(self):
+    return Ctx(self.stream, self._timer())
 
   def _upload(self):
     """{key: device copy} of the host mirrors `_host` (the entries check the host side), made on

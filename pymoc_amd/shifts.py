@@ -36,6 +36,7 @@ threshold.  include/pymoc_hip.h states the definitions; tests/shifts_cases.py re
 Out of scope: change-point models beyond the two-window statistic; more than one shift per
 series; anything across ranks, online, or on `pos`.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -43,8 +44,8 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
-from .series import _Plane, as_int, by_name
-from .windows import _DETREND, SeriesWindows, _Source, stt_of
+from .series import Ctx, View, _Plane, as_int, by_name, records
+from .windows import _DETREND, _Source, launch_windows, stt_of, win_par
 
 WHERE = ("first", "at")
 VALUES = ("stat", "jump", "before", "after")
@@ -100,7 +101,42 @@ def launch_fit_ranged(arr, shape, k0, k1, detrend, end, stream, timer, table=Non
   d.v, d.end, d.stt_tab, d.stt_tab_dev = arr.ptr, end.ptr, tab.ctypes.data, tab_dev.ptr
   with launch_span(timer, "k_series_fit_ranged", stream):
     check(lib.pm_series_fit_ranged(C.byref(d), out[0].ptr, out[1].ptr, _sh(stream)))
-  out[0]._parent._fitted = (arr, end, tab_dev)  # (they live as long as the fit read from them)
+  out[0].keep = (arr, end, tab_dev)  # (they live as long as the fit read from them)
+  return out
+
+
+Censor = collections.namedtuple("Censor", "where guard src src_dev")
+
+
+def launch_censor(x, y, cens, ctx, end_out=None):
+  """pm_series_censor with the `Censor` cens (where [nspec, n] on the device, guard, src [nspec] on
+  the host and on the device) from the device view `x` [K, nb * nspec, n] into `y` (x itself: in
+  place); the ends into `end_out` when given; nothing synchronised."""
+  d = _lib.pm_series_censor()
+  d.K, d.nspec, d.n, d.guard = x.shape[0], len(cens.src), x.shape[2], cens.guard
+  d.nb = x.shape[1] // d.nspec
+  d.x, d.where, d.src, d.src_dev = x.ptr, cens.where.ptr, cens.src.ctypes.data, cens.src_dev.ptr
+  with launch_span(ctx.timer, "k_series_censor", ctx.stream):
+    check(lib.pm_series_censor(C.byref(d), y.ptr, None if end_out is None else end_out.ptr,
+                               _sh(ctx.stream)))
+
+
+def launch_shift_scan(mean, var, nrec, k0, k1, half, thr, dirs, ctx, out=None):
+  """pm_series_shift_scan on the mean and the var plane of windows of `half` records, step 1, over
+  the records [k0, k1) of a series of nrec; thr and dirs: (host, device) [nspec].  (at, first,
+  ncand [nspec, n] int32, val [4, nspec, n]) on the device, nothing synchronised."""
+  nspec, n = mean.shape[1:]
+  d = _lib.pm_series_shift_scan()
+  d.n, d.nspec, d.nrec, d.k0, d.k1, d.half = n, nspec, nrec, k0, k1, half
+  d.mean, d.var = mean.ptr, var.ptr
+  d.thr, d.thr_dev, d.dir, d.dir_dev = (thr[0].ctypes.data, thr[1].ptr, dirs[0].ctypes.data,
+                                        dirs[1].ptr)
+  if out is None:
+    out = [DeviceArray((nspec, n), np.int32) for _ in range(3)]
+    out.append(DeviceArray((4, nspec, n), np.float64))
+  with launch_span(ctx.timer, "k_series_shift_scan", ctx.stream):
+    check(lib.pm_series_shift_scan(C.byref(d), out[0].ptr, out[1].ptr, out[2].ptr, out[3].ptr,
+                                   _sh(ctx.stream)))
   return out
 
 
@@ -166,18 +202,9 @@ class SeriesShifts(_Source):
     """pm_series_shift_scan on the two planes: (at, first, ncand [nspec, n] int32, val [4, nspec,
     n]) on the device, nothing synchronised."""
     dev = self._upload()
-    d = _lib.pm_series_shift_scan()
-    d.n, d.nspec, d.nrec, d.k0, d.k1, d.half = self.n, self.nspec, self.nrec, k0, k1, self.half
-    d.mean, d.var = mean.ptr, var.ptr
-    d.thr, d.thr_dev = self.threshold.ctypes.data, dev["thr"].ptr
-    d.dir, d.dir_dev = self.direction.ctypes.data, dev["dir"].ptr
-    if out is None:
-      out = [DeviceArray((self.nspec, self.n), np.int32) for _ in range(3)]
-      out.append(DeviceArray((4, self.nspec, self.n), np.float64))
-    with launch_span(self._timer(), "k_series_shift_scan", self.stream):
-      check(lib.pm_series_shift_scan(C.byref(d), out[0].ptr, out[1].ptr, out[2].ptr, out[3].ptr,
-                                     _sh(self.stream)))
-    return out
+    return launch_shift_scan(mean, var, self.nrec, k0, k1, self.half,
+                             (self.threshold, dev["thr"]), (self.direction, dev["dir"]),
+                             self._ctx(), out=out)
 
   def detect(self, k0=0, k1=None, max_bytes=2 << 30):
     """The shifts of the record window [k0, k1): one launch of pm_series_windows (window = half,
@@ -189,10 +216,8 @@ class SeriesShifts(_Source):
     if need > max_bytes:
       raise ValueError("the window scratch of %d bytes (32 nwin nspec n, nwin = %d) exceeds "
                        "max_bytes = %d" % (need, nwin, max_bytes))
-    sw = SeriesWindows((self._series, self.names), self.half, step=1, detrend="constant", lag=1,
-                       stream=self.stream)
-    sw._timer = self._timer
-    out, _ = sw._launch(k0, k1, nwin)
+    out, _ = launch_windows(self._series, k0, k1, win_par(self.half, 1, 1, "constant"),
+                            self._ctx())
     shape = (nwin, self.nspec, self.n)
     found = self._scan(k0, k1, _Plane(out, 0, shape), _Plane(out, 2, shape))
     self.at_dev, self.first_dev, self.ncand_dev, self.val_dev = found
@@ -202,13 +227,8 @@ class SeriesShifts(_Source):
   def _censor(self, x_ptr, K, nb, y_ptr, stream, timer, end_out=None):
     """pm_series_censor with the arguments of the last `censored` call on nb * nspec planes, on
     the caller's stream, its span where the caller's spans go."""
-    where, guard, src, src_dev = self._cens
-    d = _lib.pm_series_censor()
-    d.n, d.nspec, d.K, d.nb, d.guard = self.n, self.nspec, K, nb, guard
-    d.x, d.where, d.src, d.src_dev = x_ptr, where.ptr, src.ctypes.data, src_dev.ptr
-    with launch_span(timer, "k_series_censor", stream):
-      check(lib.pm_series_censor(C.byref(d), y_ptr, None if end_out is None else end_out.ptr,
-                                 _sh(stream)))
+    shape = (K, nb * self.nspec, self.n)
+    launch_censor(View(x_ptr, shape), View(y_ptr, shape), self._cens, Ctx(stream, timer), end_out)
 
   def censored(self, where="first", guard=0, by=None):
     """The record window of the last `detect` with NaN from every member's end on: (DeviceArray
@@ -240,13 +260,12 @@ class SeriesShifts(_Source):
     if self.nspec * K >= 1 << 31 or self.nspec * self.n >= 1 << 31:
       raise ValueError("K * nspec = %d or nspec * n = %d is not below 2^31"
                        % (self.nspec * K, self.nspec * self.n))
-    self._cens = (self.first_dev if where == "first" else self.at_dev, guard, src,
-                  DeviceArray.from_host(src, dtype=np.int32, stream=self.stream))
+    self._cens = Censor(self.first_dev if where == "first" else self.at_dev, guard, src,
+                        DeviceArray.from_host(src, dtype=np.int32, stream=self.stream))
     y = DeviceArray((K, self.nspec, self.n), np.float64)
     self.end = _Ends((self.nspec, self.n), np.int32)
     self.end._names, self.end._stream = self.names, self.stream
-    self._censor(self._series.ptr + 8 * k0 * self.nspec * self.n, K, 1, y.ptr, self.stream,
-                 self._timer(), self.end)
+    launch_censor(records(self._series, k0, k1), y, self._cens, self._ctx(), self.end)
     return y, list(self.names)
 
   def _until(self, sw, k0, k1):

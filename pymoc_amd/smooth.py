@@ -77,6 +77,34 @@ def gaussian_weights(sigma, H):
   return np.exp(-0.5 * (np.arange(H + 1, dtype=np.float64) / sigma) ** 2)
 
 
+class Weights(object):
+  """What a smoother launch takes besides the series: `half`, the table w[0 .. half] on the `host`
+  (the entry checks it there) and its device copy, uploaded once, at the first launch."""
+
+  def __init__(self, sigma, half):
+    self.half, self.host, self._dev = half, gaussian_weights(sigma, half), None
+
+  def dev(self, stream):
+    if self._dev is None:
+      self._dev = DeviceArray.from_host(self.host, dtype=np.float64, stream=stream)
+    return self._dev
+
+
+def launch_smooth(x, k0, k1, w, ctx, trend=None, resid=None, nbad=None):
+  """pm_series_smooth over the records [k0, k1) of the device view `x` with the `Weights` w, into
+  the given device arrays (trend or resid may be None): nbad [nspec, n] on the device (allocated
+  here unless given), nothing synchronised."""
+  d = _lib.pm_series_smooth()
+  (d.nrec, d.nspec, d.n), d.k0, d.k1, d.half = x.shape, k0, k1, w.half
+  d.v, d.w, d.w_dev = x.ptr, w.host.ctypes.data, w.dev(ctx.stream).ptr
+  if nbad is None:
+    nbad = DeviceArray(x.shape[1:], np.int32)
+  with launch_span(ctx.timer, "k_series_smooth", ctx.stream):
+    check(lib.pm_series_smooth(C.byref(d), None if trend is None else trend.ptr,
+                               None if resid is None else resid.ptr, nbad.ptr, _sh(ctx.stream)))
+  return nbad
+
+
 class Smoothed(object):
   """What `compute` returns: trend, resid `[name] -> [n, K]` and nbad `[name] -> [n]`."""
 
@@ -100,8 +128,8 @@ class SeriesSmooth(Series):
     if self.nspec > 65535:
       raise ValueError("nspec = %d is above 65535" % self.nspec)
     self.sigma, self.truncate, self.half = half_width(sigma, truncate)
-    self.weights = gaussian_weights(self.sigma, self.half)
-    self._host = dict(w=self.weights)
+    self._w = Weights(self.sigma, self.half)
+    self.weights = self._w.host
 
   def _window(self, k0, k1):
     k0, k1 = self._record_window(k0, k1)
@@ -113,17 +141,7 @@ class SeriesSmooth(Series):
   def _launch(self, k0, k1, trend=None, resid=None, nbad=None):
     """The launch alone into the given device arrays (trend or resid may be None): nbad on the
     device, nothing synchronised."""
-    dev = self._upload()
-    d = _lib.pm_series_smooth()
-    d.n, d.nspec, d.nrec, d.k0, d.k1, d.half = self.n, self.nspec, self.nrec, k0, k1, self.half
-    d.v, d.w, d.w_dev = self._series.ptr, self.weights.ctypes.data, dev["w"].ptr
-    if nbad is None:
-      nbad = DeviceArray((self.nspec, self.n), np.int32)
-    with launch_span(self._timer(), "k_series_smooth", self.stream):
-      check(lib.pm_series_smooth(C.byref(d), None if trend is None else trend.ptr,
-                                 None if resid is None else resid.ptr, nbad.ptr,
-                                 _sh(self.stream)))
-    return nbad
+    return launch_smooth(self._series, k0, k1, self._w, self._ctx(), trend, resid, nbad)
 
   def _alloc(self, K):
     return DeviceArray((K, self.nspec, self.n), np.float64)

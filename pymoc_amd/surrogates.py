@@ -24,7 +24,8 @@ counts by its own rule.  Under detrend "gaussian" the fit is the smoother (smoot
 the one-window "constant" fit of its residual, and the surrogates are surrogates of that residual;
 `significance` then sends every chunk through the same smoother.  With `until=` (shifts.py) the
 test runs up to every member's own end: the record window censored, the fit per member over its
-own records (pm_series_fit_ranged), every chunk censored in place.  The deviates come from the
+own records (pm_series_fit_ranged), every chunk censored in place.  The record and a chunk of
+surrogates go through the same function, `windows.indicators`.  The deviates come from the
 generator `NoiseForcing` uses; give the surrogates a seed of their own (the header says which
 coordinates would coincide).
 """
@@ -35,10 +36,10 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
-from .series import Series, _Plane, as_int, by_name
+from .series import Series, View, _Plane, as_int, by_name
 from .shifts import launch_fit_ranged
-from .smooth import SeriesSmooth
-from .windows import SeriesWindows, check_detrend, launch_kendall, residual_of, tau_b
+from .smooth import Weights
+from .windows import (alloc_windows, check_detrend, indicators, launch_kendall, tau_b, win_par)
 
 PLANES_MAX = 65535  # nb * nspec: the planes are the indices of the entries that read the series
 
@@ -72,6 +73,30 @@ def launch_exceed(obs, sur, shape, acc, stream, timer):
     check(lib.pm_series_exceed(C.byref(d), acc[0].ptr, acc[1].ptr, acc[2].ptr, _sh(stream)))
 
 
+def launch_fit(x, k0, k1, detrend, ctx, weights=None, out=None):
+  """The null model of the records [k0, k1) of the device view `x`: (var, ac), each a device
+  series [1, nspec, n] -- `windows.indicators` with ONE window of K records, lag 1 (under `weights`
+  the smoother's launch first, then the "constant" fit of its residual), nothing synchronised.
+  `out`: the window outputs of an earlier call, written again."""
+  (out, _), on = indicators(x, k0, k1, win_par(k1 - k0, 1, 1, detrend), ctx, weights=weights,
+                            out=out)
+  shape = (1,) + tuple(x.shape[1:])
+  return _Plane(out, 2, shape, keep=on[:1]), _Plane(out, 3, shape, keep=on[:1])
+
+
+def launch_surrogates(y, fit, b0, seed, member0, ctx, xi=None):
+  """pm_series_surrogates: the surrogates b0 .. b0 + nb - 1 of the fit = (var, ac) [1, nspec, n]
+  into the device view `y` [K, nb * nspec, n] (the deviates into `xi` when given); nothing
+  synchronised."""
+  d = _lib.pm_series_surrogates()
+  d.K, d.nspec, d.n, d.b0 = y.shape[0], fit[0].shape[1], y.shape[2], b0
+  d.nb = y.shape[1] // d.nspec
+  d.member0, d.seed, d.var, d.ac = member0, seed, fit[0].ptr, fit[1].ptr
+  with launch_span(ctx.timer, "k_series_surrogates", ctx.stream):
+    check(lib.pm_series_surrogates(C.byref(d), y.ptr, None if xi is None else xi.ptr,
+                                   _sh(ctx.stream)))
+
+
 class SeriesSurrogates(Series):
   """`SeriesSurrogates(source, detrend="linear", seed=0, member0=None, stream=None, sigma=None,
   truncate=4.0)`.
@@ -91,7 +116,8 @@ class SeriesSurrogates(Series):
     Series.__init__(self, source, stream)
     if self.nspec > PLANES_MAX:
       raise ValueError("nspec = %d is above %d" % (self.nspec, PLANES_MAX))
-    self._smooth, self._smoother = check_detrend(detrend, sigma, truncate), None
+    self._smooth = check_detrend(detrend, sigma, truncate)
+    self._weights = Weights(self._smooth[0], self._smooth[2]) if self._smooth else None
     self.detrend, self.seed = detrend, as_seed(seed)
     self.member0 = as_member0(member0, self._rec)
 
@@ -121,25 +147,11 @@ class SeriesSurrogates(Series):
     launch of pm_series_windows with one window of K records, lag 1, nothing synchronised.  Under
     "gaussian" the smoother's launch first, then the "constant" fit of its residual."""
     k0, k1, K = self._window(k0, k1)
-    series, detrend = self._series, self.detrend
-    if self._smooth:
-      series, detrend = residual_of(self, self._smooth, k0, k1), "constant"
-      k0, k1 = 0, K
-    one = SeriesWindows((series, self.names), K, step=1, detrend=detrend, lag=1,
-                        stream=self.stream)
-    one._timer = self._timer  # (its launch span goes where this source's spans go)
-    out, _ = one._launch(k0, k1, 1, out=out)
-    out._fitted = series  # (a residual lives as long as the fit read from it)
-    shape = (1, self.nspec, self.n)
-    return _Plane(out, 2, shape), _Plane(out, 3, shape)
+    return launch_fit(self._series, k0, k1, self.detrend, self._ctx(), self._weights, out)
 
   def _launch(self, fit, K, b0, nb, y, xi=None):
-    d = _lib.pm_series_surrogates()
-    d.n, d.nspec, d.K, d.nb, d.b0 = self.n, self.nspec, K, nb, b0
-    d.member0, d.seed, d.var, d.ac = self.member0, self.seed, fit[0].ptr, fit[1].ptr
-    with launch_span(self._timer(), "k_series_surrogates", self.stream):
-      check(lib.pm_series_surrogates(C.byref(d), y.ptr, None if xi is None else xi.ptr,
-                                     _sh(self.stream)))
+    launch_surrogates(View(y.ptr, (K, nb * self.nspec, self.n)), fit, b0, self.seed, self.member0,
+                      self._ctx(), xi)
 
   def generate(self, k0=0, k1=None, b0=0, nb=1):
     """The surrogates b0 .. b0 + nb - 1 of the record window [k0, k1): the fit, then one launch of
@@ -188,87 +200,49 @@ def chunk_size(nsur, max_bytes, K, nspec, n, per=8):
   return nb
 
 
-def censored_windows(sw, until, k0, k1):
-  """`sw` over the record window censored by `until` (shifts.py): pm_series_censor into a series of
-  K records of its own, and a `SeriesWindows` with sw's settings on it -- records [0, K)."""
-  K = k1 - k0
-  cens = DeviceArray((K, sw.nspec, sw.n), np.float64)
-  until._censor(sw._series.ptr + 8 * k0 * sw.nspec * sw.n, K, 1, cens.ptr, sw.stream,
-                sw._timer())
-  kw = dict(sigma=sw._smooth[0], truncate=sw._smooth[1]) if sw._smooth else {}
-  base = SeriesWindows((cens, sw.names), sw.window, step=sw.step, detrend=sw.detrend, lag=sw.lag,
-                       stream=sw.stream, **kw)
-  base._timer = sw._timer
-  return base
-
-
 def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None):
   """`SeriesWindows.significance` (windows.py states what it does)."""
   nsur, max_bytes = as_int("nsur", nsur), as_int("max_bytes", max_bytes)
   seed, member0 = as_seed(seed), as_member0(member0, sw._rec)
-  k0, k1, nwin = sw._window(k0, k1)
+  k0, k1, nwin = sw._trend_window(k0, k1)
   K = k1 - k0
-  if nwin > _lib.PM_KENDALL_MAX:
-    raise ValueError("the record window [%d, %d) holds %d windows, more than %d"
-                     % (k0, k1, nwin, _lib.PM_KENDALL_MAX))
   if K > _lib.PM_SURROGATE_MAX:
     raise ValueError("the record window [%d, %d) holds %d records, more than %d"
                      % (k0, k1, K, _lib.PM_SURROGATE_MAX))
   if nsur < 1:
     raise ValueError("nsur must be at least 1 (%d here)" % nsur)
-  nspec, n, stream, timer = sw.nspec, sw.n, sw.stream, sw._timer()
-  gauss = sw._smooth
-  if until is not None:  # the same test of the censored record window, a series of its own
+  nspec, n, gauss, cens = sw.nspec, sw.n, sw._weights, None
+  ctx = stream, timer = sw._ctx()
+  if until is not None:  # the same test of the censored record window
     until._until(sw, k0, k1)
+    cens = until._cens
   nbmax = chunk_size(nsur, max_bytes, K, nspec, n, per=16 if gauss else 8)
-  # 0. under "gaussian" everything below runs on the residual of the record window: records
-  #    [0, K) of a series of its own, with only the windows' means left to remove
-  if until is not None:
-    sw, k0, k1 = censored_windows(sw, until, k0, k1), 0, K
-  obs_sw, r0, r1 = sw._detrended(k0, k1)
-  gen = SeriesSurrogates((obs_sw._series, sw.names), detrend=obs_sw.detrend, seed=seed,
-                         member0=member0, stream=stream)
-  gen._timer = sw._timer
-  # 1. the observed trends
-  out, _ = obs_sw._launch(r0, r1, nwin)
+  # 1. the observed trends: `indicators` of the record window (censored into a copy)
+  (out, _), on = sw._indicators(k0, k1, cens=cens)
   shape = (nwin, nspec, n)
   obs = [launch_kendall(_Plane(out, i, shape), shape, 0, nwin, stream, timer) for i in (2, 3)]
-  # 2. the fit and the zeroed accumulators
+  # 2. the fit of what the windows were cut from (`on`), and the zeroed accumulators
+  inner = "constant" if gauss else sw.detrend  # (under "gaussian" `on` is the residual)
   if until is None:
-    fit = gen.fit(r0, r1)
+    fit = launch_fit(on[0], on[1], on[2], inner, ctx)
   else:  # per member, over its records before its end
-    fit = launch_fit_ranged(obs_sw._series, (obs_sw.nrec, nspec, n), r0, r1, obs_sw.detrend,
-                            until.end, stream, timer)
+    fit = launch_fit_ranged(on[0], on[0].shape, on[1], on[2], inner, until.end, stream, timer)
   acc = [[DeviceArray.zeros((nspec, n), np.int32, stream=stream) for _ in range(3)]
          for _ in range(2)]
-  # 3. chunk by chunk on the chunk's arrays, allocated once for the largest
-  y = DeviceArray((K, nbmax * nspec, n), np.float64)
-  yres = DeviceArray((K, nbmax * nspec, n), np.float64) if gauss else y
+  # 3. chunk by chunk on arrays allocated once for the largest: `indicators` of the surrogates
+  y =DeviceArray((K, nbmax * nspec, n), np.float64)
+  yres = DeviceArray((K, nbmax * nspec, n), np.float64) if gauss else None
   nbad = DeviceArray((nbmax * nspec, n), np.int32) if gauss else None
-  smooths = {}
-  wout = (DeviceArray((4, nwin, nbmax * nspec, n), np.float64),
-          DeviceArray((nbmax * nspec, n), np.int32))
+  wout = alloc_windows(nwin, nbmax * nspec, n)
   cnt = [DeviceArray((nbmax * nspec, n), np.int32) for _ in range(4)]
-  subs = {}
   for b0 in range(0, nsur, nbmax):
     nb = min(nbmax, nsur - b0)
     planes = nb * nspec
-    if nb not in subs:  # (at most two sizes: the chunks and the last one)
-      pnames = ["%d" % p for p in range(planes)]
-      view = _Plane(yres, 0, (K, planes, n))
-      subs[nb] = SeriesWindows((view, pnames), sw.window, step=sw.step, detrend=obs_sw.detrend,
-                               lag=sw.lag, stream=stream)
-      subs[nb]._timer = sw._timer
-      if gauss:
-        smooths[nb] = SeriesSmooth((_Plane(y, 0, (K, planes, n)), pnames), gauss[0], gauss[1],
-                                   stream=stream)
-        smooths[nb]._timer = sw._timer
-    gen._launch(fit, K, b0, nb, y)
-    if until is not None:  # cut where the record is
-      until._censor(y.ptr, K, nb, y.ptr, stream, timer)
-    if gauss:  # the same smoother the record went through
-      smooths[nb]._launch(0, K, resid=yres, nbad=nbad)
-    subs[nb]._launch(0, K, nwin, out=wout)
+    ych = _Plane(y, 0, (K, planes, n))
+    launch_surrogates(ych, fit, b0, seed, member0, ctx)
+    # (cut where the record is, in place; the same smoother the record went through)
+    indicators(ych, 0, K, sw._par, ctx, cens=cens, into=ych, weights=gauss,
+               resid=_Plane(yres, 0, ych.shape) if gauss else None, nbad=nbad, out=wout)
     wshape = (nwin, planes, n)
     for i, which in enumerate((2, 3)):
       launch_kendall(_Plane(wout[0], which, wshape), wshape, 0, nwin, stream, timer, out=cnt)

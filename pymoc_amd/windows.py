@@ -38,6 +38,11 @@ records allocated per call), and the windows are cut from the residual with only
 removed.  A record that is not finite has a NaN residual, so the windows that hold it are excluded
 as before.
 
+Every method goes through `indicators`, the one path from a device series to its indicator planes
+(censor, smooth, the window launch), and `significance` sends the record and every chunk of
+surrogates through it; `launch_windows` and `launch_kendall` are the launches alone, over any
+device view (series.py).
+
 Out of scope:
   * skewness and higher moments;
   * of the surrogate test: Fourier phase-randomised surrogates, ARMA orders above 1 (the null
@@ -47,6 +52,7 @@ Out of scope:
   * indicators of `pos` (the positions an IndexRecorder keeps next to the values);
   * linear detrending inside `SeriesSpectra`, which stays as it is.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -54,8 +60,8 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
-from .series import Series, _Plane, as_int, by_name
-from .smooth import SeriesSmooth, half_width
+from .series import Series, _Plane, as_int, by_name, records
+from .smooth import Weights, half_width, launch_smooth
 from .stats import SeriesStats
 
 _DETREND = dict(linear=_lib.PM_WIN_DETREND_LINEAR, constant=_lib.PM_WIN_DETREND_CONSTANT,
@@ -76,18 +82,6 @@ def check_detrend(detrend, sigma, truncate):
   if sigma is None:
     raise ValueError("detrend \"gaussian\" needs sigma, the kernel's width in records")
   return half_width(sigma, truncate)
-
-
-def residual_of(src, smooth, k0, k1):
-  """The smoother's launch over the records [k0, k1) of the checked source `src` with smooth =
-  (sigma, truncate, H): the residual as a device series [K, nspec, n], allocated here, nothing
-  synchronised; its launch span goes where the source's spans go."""
-  if src._smoother is None:  # (kept: the table is uploaded once per source object)
-    src._smoother = SeriesSmooth((src._series, src.names), smooth[0], smooth[1], stream=src.stream)
-    src._smoother._timer = src._timer
-  resid = src._smoother._alloc(k1 - k0)
-  src._smoother._launch(k0, k1, resid=resid)
-  return resid
 
 
 def stt_of(W):
@@ -128,6 +122,60 @@ def launch_kendall(arr, shape, k0, k1, stream, timer, out=None):
     check(lib.pm_series_kendall(C.byref(d), out[0].ptr, out[1].ptr, out[2].ptr, out[3].ptr,
                                 _sh(stream)))
   return out
+
+
+WinPar = collections.namedtuple("WinPar", "window step lag detrend stt")
+
+
+def win_par(window, step, lag, detrend):
+  """What a window launch takes besides the series; "gaussian" is "constant" here, after the
+  smoother."""
+  return WinPar(window, step, lag, _DETREND["constant" if detrend == GAUSSIAN else detrend],
+                stt_of(window))
+
+
+def alloc_windows(nwin, nspec, n):
+  """The outputs of a launch over `nwin` windows: (out [4, nwin, nspec, n], nused [nspec, n])."""
+  return DeviceArray((4, nwin, nspec, n), np.float64), DeviceArray((nspec, n), np.int32)
+
+
+def launch_windows(x, k0, k1, par, ctx, out=None):
+  """pm_series_windows over the records [k0, k1) of the device view `x` with the `WinPar` par:
+  (out [4, nwin, nspec, n], nused [nspec, n]) on the device, nothing synchronised.  `out`: the
+  arrays of an earlier call (of at least this size), written again."""
+  d = _lib.pm_series_windows()
+  (d.nrec, d.nspec, d.n), d.k0, d.k1 = x.shape, k0, k1
+  d.window, d.step, d.lag, d.detrend, d.stt = par
+  d.v = x.ptr
+  if out is None:
+    out = alloc_windows((k1 - k0 - par.window) // par.step + 1, *x.shape[1:])
+  with launch_span(ctx.timer, "k_series_windows", ctx.stream):
+    check(lib.pm_series_windows(C.byref(d), out[0].ptr, out[1].ptr, _sh(ctx.stream)))
+  return out
+
+
+def indicators(x, k0, k1, par, ctx, cens=None, into=None, weights=None, resid=None, nbad=None,
+               out=None):
+  """The one path from a device series to its indicator planes, for the record and for a chunk of
+  surrogates alike: over the records [k0, k1) of the view `x` (K records, any number of planes)
+    1. pm_series_censor with the `shifts.Censor` cens, when one is given: into `into` (x itself:
+       in place; None: a copy of K records allocated here);
+    2. pm_series_smooth with the `smooth.Weights` weights, when they are given: the residual into
+       `resid` (None: allocated here), the count into `nbad`;
+    3. pm_series_windows with `par` into `out` (as `launch_windows`).
+  Returns ((out, nused), (series, r0, r1)): the planes, and the records the windows were cut from,
+  which a null-model fit reads.  Nothing is synchronised."""
+  K, planes = k1 - k0, tuple(x.shape[1:])
+  if cens is not None:
+    from .shifts import launch_censor  # (shifts derives from this module)
+    into = DeviceArray((K,) + planes, np.float64) if into is None else into
+    launch_censor(records(x, k0, k1), into, cens, ctx)
+    x, k0, k1 = into, 0, K
+  if weights is not None:
+    resid = DeviceArray((K,) + planes, np.float64) if resid is None else resid
+    launch_smooth(x, k0, k1, weights, ctx, resid=resid, nbad=nbad)
+    x, k0, k1 = resid, 0, K
+  return launch_windows(x, k0, k1, par, ctx, out=out), (x, k0, k1)
 
 
 class Trend(object):
@@ -203,9 +251,10 @@ class SeriesWindows(_Source):
       raise ValueError("step must lie in [1, window = %d] (%d here)" % (W, S))
     if not 1 <= Lg <= W - 2:
       raise ValueError("lag must lie in [1, window - 2 = %d] (%d here)" % (W - 2, Lg))
-    self._smooth, self._smoother = check_detrend(detrend, sigma, truncate), None
-    self.window, self.step, self.lag, self.detrend = W, S, Lg, detrend
-    self.stt = stt_of(W)
+    self._smooth = check_detrend(detrend, sigma, truncate)
+    self._weights = Weights(self._smooth[0], self._smooth[2]) if self._smooth else None
+    self._par = win_par(W, S, Lg, detrend)
+    self.window, self.step, self.lag, self.detrend, self.stt = W, S, Lg, detrend, self._par.stt
     self._set_groups(groups)  # checked now, used by across_members
 
   def _window(self, k0, k1):
@@ -230,39 +279,28 @@ class SeriesWindows(_Source):
     k0, k1, nwin = self._window(k0, k1)
     return k0 + np.arange(nwin) * self.step + self.window - 1
 
-  def _alloc(self, nwin):
-    """The outputs of a launch over `nwin` windows: (out [4, nwin, nspec, n], nused [nspec, n])."""
-    return (DeviceArray((4, nwin, self.nspec, self.n), np.float64),
-            DeviceArray((self.nspec, self.n), np.int32))
+  def _trend_window(self, k0, k1):
+    """`_window` where the indicator series goes through pm_series_kendall."""
+    k0, k1, nwin = self._window(k0, k1)
+    if nwin > _lib.PM_KENDALL_MAX:
+      raise ValueError("the record window [%d, %d) holds %d windows, more than %d"
+                       % (k0, k1, nwin, _lib.PM_KENDALL_MAX))
+    return k0, k1, nwin
 
-  def _detrended(self, k0, k1):
-    """(sw, k0, k1): what the window launch runs on.  This object and its record window; under
-    "gaussian" the smoother's launch, then a `SeriesWindows` with detrend "constant" over the
-    records [0, K) of the residual series."""
-    if not self._smooth:
-      return self, k0, k1
-    sub = SeriesWindows((residual_of(self, self._smooth, k0, k1), self.names), self.window,
-                        step=self.step, detrend="constant", lag=self.lag, stream=self.stream)
-    sub._timer = self._timer
-    return sub, 0, k1 - k0
+  def _alloc(self, nwin):
+    return alloc_windows(nwin, self.nspec, self.n)
 
   def _launch(self, k0, k1, nwin, out=None):
-    """The launch alone: (out [4, nwin, nspec, n], nused [nspec, n]) on the device, nothing
-    synchronised.  `out`: the arrays of an earlier call, written again."""
-    d = _lib.pm_series_windows()
-    d.n, d.nspec, d.nrec, d.k0, d.k1 = self.n, self.nspec, self.nrec, k0, k1
-    d.window, d.step, d.lag, d.detrend = self.window, self.step, self.lag, _DETREND[self.detrend]
-    d.v, d.stt = self._series.ptr, self.stt
-    if out is None:
-      out = self._alloc(nwin)
-    with launch_span(self._timer(), "k_series_windows", self.stream):
-      check(lib.pm_series_windows(C.byref(d), out[0].ptr, out[1].ptr, _sh(self.stream)))
-    return out
+    """The window launch alone on the source series, nothing synchronised: `launch_windows`."""
+    return launch_windows(self._series, k0, k1, self._par, self._ctx(), out=out)
+
+  def _indicators(self, k0, k1, **kw):
+    """`indicators` of the source series with this object's settings."""
+    return indicators(self._series, k0, k1, self._par, self._ctx(), weights=self._weights, **kw)
 
   def compute(self, k0=0, k1=None):
     k0, k1, nwin = self._window(k0, k1)
-    sw, r0, r1 = self._detrended(k0, k1)
-    out, nused = sw._launch(r0, r1, nwin)
+    (out, nused), _ = self._indicators(k0, k1)
     return Windows(self.names, k0 + np.arange(nwin) * self.step + self.window - 1,
                    out.download(stream=self.stream), nused.download(stream=self.stream))
 
@@ -280,20 +318,15 @@ class SeriesWindows(_Source):
     st = SeriesStats((view, self.names), groups=self.groups, quantiles=quantiles,
                      stream=self.stream)
     self.group_labels = st.group_labels
-    sw, r0, r1 = self._detrended(k0, k1)
-    sw._launch(r0, r1, nwin, out=out)
+    self._indicators(k0, k1, out=out)
     return st.across_members()
 
   def trend(self, k0=0, k1=None):
     """Kendall's tau against time of the var and of the ac series of every (index, member): the
     launch, then pm_series_kendall over out[2] and out[3] on the device.  NaN windows (unused, or
     ac of a window without variance) are left out of the pairs and show in nfin."""
-    k0, k1, nwin = self._window(k0, k1)
-    if nwin > _lib.PM_KENDALL_MAX:
-      raise ValueError("the record window [%d, %d) holds %d windows, more than %d"
-                       % (k0, k1, nwin, _lib.PM_KENDALL_MAX))
-    sw, r0, r1 = self._detrended(k0, k1)
-    out, _ = sw._launch(r0, r1, nwin)
+    k0, k1, nwin = self._trend_window(k0, k1)
+    (out, _), _ = self._indicators(k0, k1)
     shape = (nwin, self.nspec, self.n)
     res = []
     for i in (2, 3):
