@@ -909,10 +909,68 @@ __device__ __forceinline__ int conv_spec_run(const ColGrid<P> &g, ColRegs<P> &r,
     }
     pos = s_end;
   };
+  // The twin's UNR-step tier, with SUPER-BLOCKS in front of it: a super-block is SUP passes of a
+  // ROLLED loop over the one UNR-fold unrolled body, begun and checked once -- the check (7 vector +
+  // 17 scalar instructions in the filter loops) is paid once per 64 steps instead of per 16, and the
+  // pass counter is the rolled loop's only loop-carried scalar (3 scalar instructions per pass).
+  // Both block lengths run in ONE loop nest, the passes of a block being a scalar of the block
+  // loop, so that each variant keeps a single unrolled body: a kernel half as large again was
+  // slower elsewhere (see column_steps_body).  Super-blocks run where at least 4 of them are to go
+  // (read once, at entry, as the UNR-step tier reads its threshold), the UNR-step blocks after them; a bad super-block is redone whole by the same redo().
+  auto tier_rolled = [&]() {
+    constexpr int N = UNR, SUP = 4;
+    const int togo = nsteps - pos;
+    const int n_sup = togo >= 4 * SUP * N ? togo / (SUP * N) : 0;
+    const int n_blk = togo >= 4 * N ? (togo - n_sup * SUP * N) / N : 0;
+    const int s_end = pos + (n_sup * SUP + n_blk) * N;
+    for (int left = n_sup + n_blk; left > 0; --left) {
+      const int passes = left > n_blk ? SUP : 1;
+      block_begin();
+      int q = passes;
+#pragma nounroll
+      do {
+        // Where the body lies on the 64-byte lines of the instruction fetch: it is runs of 8-byte
+        // instructions (the 4-byte v_fmac_f64_e32 come in close pairs), so either a handful of them
+        // cross a line or three lines in four begin inside one, as the code in front of the loop
+        // has it -- and a lone wave has nothing to hide the fetch behind: the filter loop of form 7
+        // took 70.1 us per 1000 steps in the second position where the instruction model gives 67.0.  The filter loops (the headline's slowest
+        // waves run them) therefore put their pass on 8-byte addresses: padding to 8 bytes, then two
+        // 4-byte s_nop -- this one and the one the compiler puts behind every asm that writes a
+        // VGPR.  Tied to imax so that it stays in front of the pass's first v_max3_i32; at most 3
+        // slots per 16 steps.  tests/test_column_loop_placement_cpu.py fails when a build's passes lie otherwise.
+        if constexpr (IF != 0) asm volatile(".p2align 3\n\ts_nop 0" : "+v"(imax));
+#pragma unroll
+        for (int k = 0; k < N; ++k) spec();
+      } while (--q > 0);
+      if (__builtin_expect(block_bad(), 0)) {
+        redo(passes * N);
+        bool leave;
+        if constexpr (IF != 0) {
+          cls.filt = false;
+          leave = true;
+        } else {
+          leave = cls.surf != 0 || conv_variant<P>(cc) != SEL || conv_surface_only<P>(cc, nz);  // (as in tier)
+        }
+        if (leave) {
+          // the steps of the blocks behind this one: super-blocks first, then the n_blk short ones
+          const int behind = left > n_blk ? ((left - 1 - n_blk) * SUP + n_blk) * N : (left - 1) * N;
+          ret = s_end - behind;
+          left = 1;
+        } else {
+          set_adj();
+        }
+      }
+    }
+    pos = s_end;
+  };
   // the long blocks only in long launches: a pattern change redoes the whole block, and the
   // coupled drivers' 24-step launches (new forcing, hence often a new pattern, every launch)
   // came out 9 % slower with them
-  if (UNR <= 4 || nsteps - pos >= 4 * UNR) tier(std::integral_constant<int, UNR>{});
+  if constexpr (CLS && P <= 2) {
+    tier_rolled();
+  } else {
+    if (UNR <= 4 || nsteps - pos >= 4 * UNR) tier(std::integral_constant<int, UNR>{});
+  }
   if (ret >= 0) return ret;
   if constexpr (UNR > 4) {
     tier(std::integral_constant<int, 4>{});
