@@ -1619,6 +1619,98 @@ struct pm_series_fit_ranged {
 int pm_series_fit_ranged(const struct pm_series_fit_ranged *d, double *var, double *ac,
                          pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fourier phase-randomised surrogates of a recorded series (pymoc_amd.SeriesSurrogates(method =
+ * "fourier"), SeriesWindows.significance(method = "fourier")), on the device: ONE launch per entry
+ * and chunk of surrogates.  (no counterpart: what a user does with numpy.fft.rfft / irfft and a
+ * loop over the downloaded series.)  A surrogate keeps the whole periodogram of the detrended
+ * record window and randomises only the phases: the null model where the series is not AR(1).
+ * Every product and sum is rounded on its own (-ffp-contract=off), and the device calls no sin,
+ * cos, exp or sqrt: every trigonometric value comes from a table the caller passes, so a NumPy
+ * restatement that reads the same arrays gives every double bit for bit.
+ *
+ * K = the records of the window, PM_WIN_MIN = 4 <= K <= PM_SURROGATE_MAX = 4096 (any K);
+ * M = the smallest power of two with M >= 2K - 1 and M >= 8, so 8 <= M <= 8192.
+ * Tables (each [..][2]: re, im), made once per K on the host:
+ *   tw[M/2]     (cos(2 pi j / M), -sin(2 pi j / M)): pm_series_spectra's table at L = M
+ *   chirp[K]    (cos(pi q / K), -sin(pi q / K)), q = j^2 mod 2K taken in integers
+ *   filt[M]     the transform FFT_M below, in float64 with the same table tw, of b:
+ *               b_j = conj(chirp_j) for j < K, b_{M-j} = b_j for 1 <= j < K, +0 elsewhere
+ *   ph_hi[256]  e^{2 pi i a / 256};   ph_lo[256]  e^{2 pi i c / 65536}
+ * The complex product x * c is  re = x.re*c.re - x.im*c.im,  im = x.re*c.im + x.im*c.re.
+ * FFT_M(a) is the iterative radix-2 decimation-in-time transform exactly as stated for
+ * pm_series_spectra above, of a complex a: a'[j] = a[bitrev(j)], then the stages h = 1 .. M/2 with
+ * W = tw[q * (M / (2h))].
+ *
+ * BLU(x, sigma), the DFT of length K of a complex x with sign sigma (-1 forward, +1 inverse), by
+ * Bluestein's chirp-z.  c^ = chirp for sigma = -1 and its conjugate for +1; B^ = filt, or its
+ * conjugate, likewise (both conjugations exact; b is even, so its transform is even):
+ *   a_j = x_j * c^_j for j < K, +0 for K <= j < M
+ *   A   = FFT_M(a);   C_k = A_k * B^_k
+ *   c   = conj(FFT_M(conj(C))) * (1 / M)           (a power of two)
+ *   X_k = c_k * c^_k for k < K
+ * (An implementation may fuse stages, skip work on known zeros or reorder independent operations
+ * as long as it reproduces these bits.)
+ *
+ * pm_series_fourier_coef -- per (index s, member m) over the record window [k0, k1) of the series
+ * v[k][s][m]: if any of the K records is not finite (isfinite) every coefficient of that series
+ * is NaN.  Otherwise r_j is exactly the r_j pm_series_windows defines for ONE window of W = K
+ * records under `detrend` (PM_WIN_DETREND_NONE, _CONSTANT or _LINEAR: the same sequential pass-1
+ * sums, mean and slope; stt = K (K^2 - 1) / 12 is checked against the entry's own value), and
+ *   R = BLU(r + 0i, -1);   coef[0][f][s][m] = R_f.re,  coef[1][f][s][m] = R_f.im,  f < nf = K/2 + 1
+ * Each of the two planes is itself a series [nf][nspec][n] in the layout above.
+ *
+ * pm_series_surrogates_fourier -- per (surrogate b = b0 + i, s, m), written as y[j][i*nspec+s][m],
+ * the layout of pm_series_surrogates:
+ *   Z_0 = (R_0.re, +0);  for even K  Z_{K/2} = (R_{K/2}.re, +0);  for 1 <= f <= (K - 1) / 2:
+ *     q = the top 16 bits of output word 0 of Philox4x32-10 keyed by the seed with the counter
+ *         words { id_lo, id_hi, b, (s << 12) | f }, id = member0 + m  (f <= 2047: the packing is
+ *         one to one)
+ *     E = ph_hi[q >> 8] * ph_lo[q & 255];   Z_f = R_f * E;   Z_{K-f} = conj(Z_f)
+ *   y_j = BLU(Z, +1)_j.re / (double)K
+ * The phase is rotated, not replaced: |Z_f| = |R_f| up to rounding, without a sqrt; it is one of
+ * 65536 values.  The counter is the one of pm_series_surrogates' deviate xi_f of the same
+ * (seed, member, b, s): under the same seed the phase of frequency f and the AR(1) deviate of
+ * record f come from the same Philox output (the phase from word 0's top 16 bits, the deviate
+ * from all four words); give the two kinds of surrogate seeds of their own where that matters,
+ * and a NoiseForcing too, as stated there.  A series with NaN coefficients has K NaN records:
+ * stored, never skipped.  A surrogate depends on nothing but (seed, member0 + m, b, s) and that
+ * series' coefficients: not on n, the shard, the chunk [b0, b0 + nb) or the launch geometry.
+ * scratch (may be NULL) is a device array of y's size that must not overlap y: with one the entry
+ * stores every series contiguously there and transposes it into y in a second launch -- the same
+ * values, another store order, faster where a block holds a single series (M >= 2048); what scratch
+ * holds afterwards is unspecified.
+ *
+ * Checked before the launch (PM_EINVAL, outputs untouched): no NULL pointer (but scratch); n, nspec >= 1 and
+ * nrec >= 1, 0 <= k0 < k1 <= nrec (coef) or nb >= 1 (surrogates); PM_WIN_MIN <= K <=
+ * PM_SURROGATE_MAX; M equal to the entry's own value for K; a known detrend and stt equal to the
+ * entry's own value (coef); b0 >= 0, b0 + nb <= 2^32 and member0 >= 0; nspec <= 65535 and
+ * nspec * n < 2^31 (coef); nb * nspec <= 65535, K * nb * nspec < 2^31 and nb * nspec * n < 2^31
+ * (surrogates); every entry of the HOST mirrors of the tables finite.  The checks read the host
+ * tables; the kernels read the device copies of the same values.                                */
+struct pm_series_fourier_coef {
+  int32_t n, nspec, nrec, k0, k1, detrend, M, reserved;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  double stt;                            /* K (K^2 - 1) / 12                                      */
+  const double *tw, *chirp, *filt;       /* HOST [M/2][2], [K][2], [M][2]                         */
+  const double *tw_dev, *chirp_dev, *filt_dev;   /* DEVICE, the same values                       */
+};
+int pm_series_fourier_coef(const struct pm_series_fourier_coef *d, double *coef,
+                           pm_stream_t stream);
+struct pm_series_surrogates_fourier {
+  int32_t n, nspec, K, nb;
+  int64_t b0;                            /* the GLOBAL number of the chunk's first surrogate      */
+  int64_t member0;                       /* the GLOBAL number of member 0                         */
+  uint64_t seed;
+  int32_t M, reserved;
+  const double *coef;                    /* device [2][K/2 + 1][nspec][n]                         */
+  const double *tw, *chirp, *filt, *ph_hi, *ph_lo;   /* HOST [M/2][2], [K][2], [M][2], [256][2] x2 */
+  const double *tw_dev, *chirp_dev, *filt_dev, *ph_hi_dev, *ph_lo_dev;   /* DEVICE, the same      */
+  double *scratch;                       /* device [nb * nspec * n][K], or NULL                   */
+};
+int pm_series_surrogates_fourier(const struct pm_series_surrogates_fourier *d, double *y,
+                                 pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

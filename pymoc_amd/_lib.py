@@ -415,6 +415,26 @@ class pm_series_fit_ranged(C.Structure):
               ("stt_tab_dev", c_dp)]
 
 
+class pm_series_fourier_coef(C.Structure):
+  """Mirror of `struct pm_series_fourier_coef` (include/pymoc_hip.h); `tw`, `chirp` and `filt` are
+  HOST addresses."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("detrend", C.c_int32), ("M", C.c_int32), ("reserved", C.c_int32),
+              ("v", c_dp), ("stt", C.c_double), ("tw", C.c_void_p), ("chirp", C.c_void_p),
+              ("filt", C.c_void_p), ("tw_dev", c_dp), ("chirp_dev", c_dp), ("filt_dev", c_dp)]
+
+
+class pm_series_surrogates_fourier(C.Structure):
+  """Mirror of `struct pm_series_surrogates_fourier` (include/pymoc_hip.h); `tw`, `chirp`, `filt`,
+  `ph_hi` and `ph_lo` are HOST addresses."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("K", C.c_int32), ("nb", C.c_int32),
+              ("b0", C.c_int64), ("member0", C.c_int64), ("seed", C.c_uint64), ("M", C.c_int32),
+              ("reserved", C.c_int32), ("coef", c_dp), ("tw", C.c_void_p), ("chirp", C.c_void_p),
+              ("filt", C.c_void_p), ("ph_hi", C.c_void_p), ("ph_lo", C.c_void_p), ("tw_dev", c_dp),
+              ("chirp_dev", c_dp), ("filt_dev", c_dp), ("ph_hi_dev", c_dp), ("ph_lo_dev", c_dp),
+              ("scratch", c_dp)]
+
+
 if not os.path.exists(LIB_PATH):
   raise ImportError(
       "pymoc_amd: %s is missing. Build it with `make lib` (hipcc --offload-arch=gfx950) "
@@ -543,6 +563,9 @@ SIGNATURES = {
                                        C.c_void_p]),
     "pm_series_censor": (C.c_int, [C.POINTER(pm_series_censor), c_dp, c_dp, C.c_void_p]),
     "pm_series_fit_ranged": (C.c_int, [C.POINTER(pm_series_fit_ranged), c_dp, c_dp, C.c_void_p]),
+    "pm_series_fourier_coef": (C.c_int, [C.POINTER(pm_series_fourier_coef), c_dp, C.c_void_p]),
+    "pm_series_surrogates_fourier": (C.c_int, [C.POINTER(pm_series_surrogates_fourier), c_dp,
+                                               C.c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

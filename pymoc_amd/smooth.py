@@ -28,7 +28,7 @@ Out of scope:
   * skewness and higher moments;
   * other kernels (Epanechnikov, loess) -- the entry takes any non-increasing positive table, this
     class forms the Gaussian one;
-  * Fourier phase-randomised surrogates, ARMA orders above 1;
+  * ARMA orders above 1;
   * record windows of more than 4096 records;
   * smoothing across ranks: every rank treats its own members;
   * online smoothing: the series is smoothed after the samples;

@@ -1,5 +1,6 @@
-"""SeriesSurrogates: stationary AR(1) surrogates of a recorded index series, generated on the
-device, and the counting behind `SeriesWindows.significance`.
+"""SeriesSurrogates: stationary AR(1) surrogates, or Fourier phase-randomised surrogates, of a
+recorded index series, generated on the device, and the counting behind
+`SeriesWindows.significance`.
 
 Kendall's tau of a sliding-window indicator means nothing by itself: overlapping windows make the
 indicator series strongly serially correlated, and stationary red noise routinely gives |tau| of
@@ -28,20 +29,57 @@ own records (pm_series_fit_ranged), every chunk censored in place.  The record a
 surrogates go through the same function, `windows.indicators`.  The deviates come from the
 generator `NoiseForcing` uses; give the surrogates a seed of their own (the header says which
 coordinates would coincide).
+
+`method="fourier"` is the nonparametric null of the same papers: a surrogate keeps the whole
+periodogram of the detrended record window and randomises only the phases, the null model of
+choice where the index is not AR(1) (a spectral peak, a band-limited response).  In place of the
+fit, pm_series_fourier_coef (csrc/fourier.hip) takes the DFT of the window's residual -- any K,
+by Bluestein's chirp-z held in LDS -- and pm_series_surrogates_fourier rotates every coefficient
+by a phase drawn from the same Philox generator and transforms back, into the same layout
+[K, nb * nspec, n]; everything downstream is unchanged.  From 513 records on (M >= 2048, where a
+block of the synthesis holds one series) the entry is given a scratch array of the chunk's size to
+store series-contiguously and transpose from; `significance` counts it against max_bytes.
+
+  coefficients(k0, k1)      the device planes (re, im), each [K / 2 + 1, nspec, n], of the DFT of
+                            the record window's residual
+  generate(k0, k1, b0, nb)  as above; `fit()` raises
+
+The phase of a coefficient is one of 65536 values (the product of two table entries: the device
+evaluates no sin or cos, so tests/fourier_cases.py restates every double bit for bit on the
+tables of fourier.py, which are cached per K on the object).  Under "gaussian" the coefficients
+are the "constant" coefficients of the smoother's residual, the composition the AR(1) fit uses.
+A series with a non-finite record has NaN coefficients and NaN surrogates; a constant series has
+zero coefficients and zero surrogates, whose indicators have no trend to count.
+
+Out of scope for method="fourier": `until=` (the transform length would be each member's own),
+amplitude-adjusted (AAFT / IAAFT) surrogates, packing two surrogates into one complex transform,
+K > 4096, anything across ranks or online, and surrogates of `pos`.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
+from . import fourier
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
 from .series import Series, View, _Plane, as_int, by_name
 from .shifts import launch_fit_ranged
-from .smooth import Weights
+from .smooth import Weights, launch_smooth
 from .windows import (alloc_windows, check_detrend, indicators, launch_kendall, tau_b, win_par)
 
 PLANES_MAX = 65535  # nb * nspec: the planes are the indices of the entries that read the series
+METHODS = ("ar1", "fourier")
+
+
+def check_method(method, until=None):
+  """A null model's name; "fourier" takes no `until`."""
+  if method not in METHODS:
+    raise ValueError("unknown method %r (one of %s)" % (method, ", ".join(METHODS)))
+  if method == "fourier" and until is not None:
+    raise ValueError("method \"fourier\" does not take until=: every member would be cut at an "
+                     "end of its own, so the transform length would be each member's own")
+  return method
 
 
 def as_seed(seed):
@@ -97,9 +135,23 @@ def launch_surrogates(y, fit, b0, seed, member0, ctx, xi=None):
                                    _sh(ctx.stream)))
 
 
+def launch_coefficients(x, k0, k1, detrend, tab, ctx, weights=None, out=None):
+  """The Fourier coefficients of the records [k0, k1) of the device view `x` under the class
+  detrend `detrend`: the device array [2, K / 2 + 1, nspec, n] of pm_series_fourier_coef (under
+  `weights` the smoother's launch first, then the "constant" coefficients of its residual),
+  nothing synchronised.  `out`: the array of an earlier call, written again."""
+  K = k1 - k0
+  if weights is not None:
+    resid = DeviceArray((K,) + tuple(x.shape[1:]), np.float64)
+    launch_smooth(x, k0, k1, weights, ctx, resid=resid)
+    x, k0, k1 = resid, 0, K
+  par = win_par(K, 1, 1, detrend)
+  return fourier.launch_coef(x, k0, k1, par.detrend, par.stt, tab, ctx, out=out)
+
+
 class SeriesSurrogates(Series):
   """`SeriesSurrogates(source, detrend="linear", seed=0, member0=None, stream=None, sigma=None,
-  truncate=4.0)`.
+  truncate=4.0, method="ar1")`.
 
   source    an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
   detrend   what the fit removes from the record window first: "linear", "constant", "none", or
@@ -108,12 +160,15 @@ class SeriesSurrogates(Series):
   seed      of the deviates, in [0, 2^64)
   member0   the global number of member 0; None: the recorder's ensemble's (what its NoiseForcing
             is bound with), 0 for a tuple source
+  method    "ar1": stationary AR(1) surrogates of the fit; "fourier": phase-randomised surrogates
+            of the residual's DFT (the phase one of 65536 values)
 
   A record window [k0, k1) holds K records, 4 <= K <= 4096."""
 
   def __init__(self, source, detrend="linear", seed=0, member0=None, stream=None, sigma=None,
-               truncate=4.0):
+               truncate=4.0, method="ar1"):
     Series.__init__(self, source, stream)
+    self.method, self._tables = check_method(method), {}
     if self.nspec > PLANES_MAX:
       raise ValueError("nspec = %d is above %d" % (self.nspec, PLANES_MAX))
     self._smooth = check_detrend(detrend, sigma, truncate)
@@ -146,8 +201,29 @@ class SeriesSurrogates(Series):
     """The null model of the record window: (var, ac), each a device series [1, nspec, n] -- one
     launch of pm_series_windows with one window of K records, lag 1, nothing synchronised.  Under
     "gaussian" the smoother's launch first, then the "constant" fit of its residual."""
+    if self.method != "ar1":
+      raise ValueError("method %r has no fit: see coefficients()" % (self.method,))
     k0, k1, K = self._window(k0, k1)
     return launch_fit(self._series, k0, k1, self.detrend, self._ctx(), self._weights, out)
+
+  def tables(self, K):
+    """The `fourier.Tables` of K records, made once per K."""
+    return fourier.tables_of(self._tables, K)
+
+  def _coefficients(self, k0, k1, K):
+    return launch_coefficients(self._series, k0, k1, self.detrend, self.tables(K), self._ctx(),
+                               self._weights)
+
+  def coefficients(self, k0=0, k1=None):
+    """method="fourier": the DFT of the record window's residual, (re, im), each a device series
+    [K / 2 + 1, nspec, n] -- one launch of pm_series_fourier_coef, nothing synchronised.  Under
+    "gaussian" the smoother's launch first, then the "constant" coefficients of its residual."""
+    if self.method != "fourier":
+      raise ValueError("method %r has no coefficients: see fit()" % (self.method,))
+    k0, k1, K = self._window(k0, k1)
+    coef = self._coefficients(k0, k1, K)
+    shape = (K // 2 + 1, self.nspec, self.n)
+    return _Plane(coef, 0, shape), _Plane(coef, 1, shape)
 
   def _launch(self, fit, K, b0, nb, y, xi=None):
     launch_surrogates(View(y.ptr, (K, nb * self.nspec, self.n)), fit, b0, self.seed, self.member0,
@@ -155,12 +231,18 @@ class SeriesSurrogates(Series):
 
   def generate(self, k0=0, k1=None, b0=0, nb=1):
     """The surrogates b0 .. b0 + nb - 1 of the record window [k0, k1): the fit, then one launch of
-    pm_series_surrogates.  Returns (DeviceArray [K, nb * nspec, n], names), a source of its own
-    (pass `stream=` this object's stream with it)."""
+    pm_series_surrogates (method="fourier": the coefficients, then one launch of
+    pm_series_surrogates_fourier).  Returns (DeviceArray [K, nb * nspec, n], names), a source of
+    its own (pass `stream=` this object's stream with it)."""
     k0, k1, K = self._window(k0, k1)
     b0, nb = self._chunk(b0, nb)
-    fit = self.fit(k0, k1)
     y = DeviceArray((K, nb * self.nspec, self.n), np.float64)
+    if self.method == "fourier":
+      scratch = DeviceArray(y.shape, np.float64) if fourier.wants_scratch(K) else None
+      fourier.launch_synthesis(y, self._coefficients(k0, k1, K), self.nspec, b0, self.seed,
+                               self.member0, self.tables(K), self._ctx(), scratch)
+      return y, self.names_of(b0, nb)
+    fit = self.fit(k0, k1)
     self._launch(fit, K, b0, nb, y)
     return y, self.names_of(b0, nb)
 
@@ -200,8 +282,9 @@ def chunk_size(nsur, max_bytes, K, nspec, n, per=8):
   return nb
 
 
-def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None):
+def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None, method="ar1"):
   """`SeriesWindows.significance` (windows.py states what it does)."""
+  check_method(method, until)
   nsur, max_bytes = as_int("nsur", nsur), as_int("max_bytes", max_bytes)
   seed, member0 = as_seed(seed), as_member0(member0, sw._rec)
   k0, k1, nwin = sw._trend_window(k0, k1)
@@ -216,14 +299,20 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None):
   if until is not None:  # the same test of the censored record window
     until._until(sw, k0, k1)
     cens = until._cens
-  nbmax = chunk_size(nsur, max_bytes, K, nspec, n, per=16 if gauss else 8)
+  # (a Fourier chunk of more than 512 records holds a second array to transpose from: under
+  # "gaussian" the residual's, which the smoother writes afterwards)
+  two = method == "fourier" and fourier.wants_scratch(K)
+  nbmax = chunk_size(nsur, max_bytes, K, nspec, n, per=16 if gauss or two else 8)
   # 1. the observed trends: `indicators` of the record window (censored into a copy)
   (out, _), on = sw._indicators(k0, k1, cens=cens)
   shape = (nwin, nspec, n)
   obs = [launch_kendall(_Plane(out, i, shape), shape, 0, nwin, stream, timer) for i in (2, 3)]
   # 2. the fit of what the windows were cut from (`on`), and the zeroed accumulators
   inner = "constant" if gauss else sw.detrend  # (under "gaussian" `on` is the residual)
-  if until is None:
+  if method == "fourier":  # in place of the fit: the coefficients of the same records
+    tab = fourier.tables_of(sw._fourier_tables, K)  # (K >= W >= PM_WIN_MIN)
+    coef = launch_coefficients(on[0], on[1], on[2], inner, tab, ctx)
+  elif until is None:
     fit = launch_fit(on[0], on[1], on[2], inner, ctx)
   else:  # per member, over its records before its end
     fit = launch_fit_ranged(on[0], on[0].shape, on[1], on[2], inner, until.end, stream, timer)
@@ -231,7 +320,7 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None):
          for _ in range(2)]
   # 3. chunk by chunk on arrays allocated once for the largest: `indicators` of the surrogates
   y =DeviceArray((K, nbmax * nspec, n), np.float64)
-  yres = DeviceArray((K, nbmax * nspec, n), np.float64) if gauss else None
+  yres = DeviceArray((K, nbmax * nspec, n), np.float64) if gauss or two else None
   nbad = DeviceArray((nbmax * nspec, n), np.int32) if gauss else None
   wout = alloc_windows(nwin, nbmax * nspec, n)
   cnt = [DeviceArray((nbmax * nspec, n), np.int32) for _ in range(4)]
@@ -239,7 +328,10 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None):
     nb = min(nbmax, nsur - b0)
     planes = nb * nspec
     ych = _Plane(y, 0, (K, planes, n))
-    launch_surrogates(ych, fit, b0, seed, member0, ctx)
+    if method == "fourier":
+      fourier.launch_synthesis(ych, coef, nspec, b0, seed, member0, tab, ctx, yres if two else None)
+    else:
+      launch_surrogates(ych, fit, b0, seed, member0, ctx)
     # (cut where the record is, in place; the same smoother the record went through)
     indicators(ych, 0, K, sw._par, ctx, cens=cens, into=ych, weights=gauss,
                resid=_Plane(yres, 0, ych.shape) if gauss else None, nbad=nbad, out=wout)

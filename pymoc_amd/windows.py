@@ -18,7 +18,8 @@ number in one more (pm_series_kendall); only the results are downloaded.
                            downloaded
   kendall(source, k0, k1)  the same counts and tau of any device series
   significance(k0, k1, nsur)
-                           the surrogate test of `trend`: AR(1) surrogates generated on the device
+                           the surrogate test of `trend`: AR(1) surrogates (or, method="fourier",
+                           Fourier phase-randomised ones) generated on the device
                            (surrogates.py), each through the same two launches, and a counting
                            launch; p_rising, p_falling and the three counts [name] -> [n];
                            `until=`: up to every member's own end (shifts.py)
@@ -45,8 +46,9 @@ device view (series.py).
 
 Out of scope:
   * skewness and higher moments;
-  * of the surrogate test: Fourier phase-randomised surrogates, ARMA orders above 1 (the null
-    model is AR(1)), and surrogates of `pos`;
+  * of the surrogate test: ARMA orders above 1 (the parametric null model is AR(1)), `until=`
+    with Fourier surrogates, amplitude-adjusted (AAFT / IAAFT) surrogates, and surrogates of
+    `pos`;
   * anything across ranks: every rank treats its own members;
   * anything online: the indicators are computed from the recorded series, after the samples;
   * indicators of `pos` (the positions an IndexRecorder keeps next to the values);
@@ -254,6 +256,7 @@ class SeriesWindows(_Source):
     self._smooth = check_detrend(detrend, sigma, truncate)
     self._weights = Weights(self._smooth[0], self._smooth[2]) if self._smooth else None
     self._par = win_par(W, S, Lg, detrend)
+    self._fourier_tables = {}  # per K, for significance(method="fourier")
     self.window, self.step, self.lag, self.detrend, self.stt = W, S, Lg, detrend, self._par.stt
     self._set_groups(groups)  # checked now, used by across_members
 
@@ -335,7 +338,7 @@ class SeriesWindows(_Source):
     return WindowTrend(*res)
 
   def significance(self, k0=0, k1=None, nsur=1000, seed=0, member0=None, max_bytes=2 << 30,
-                   until=None):
+                   until=None, method="ar1"):
     """The surrogate test of `trend()`: `nsur` stationary AR(1) surrogates of every series, fitted
     to the record window under this object's detrend (surrogates.py), each through the identical
     window + Kendall pipeline, all on the device.  Returns a `surrogates.Significance`: `.var` and
@@ -362,7 +365,18 @@ class SeriesWindows(_Source):
     pm_series_fit_ranged over every member's records [k0, k0 + end) (of the censored series, or of
     its residual with "constant"), and every chunk goes through pm_series_censor in place, with
     the same ends, between pm_series_surrogates and what follows: a surrogate is cut where the
-    record is.  Without `until` the launches are the ones listed above."""
+    record is.  Without `until` the launches are the ones listed above.
+
+    `method`: "ar1" (the default: everything above) or "fourier", the nonparametric null: the fit
+    is replaced by one launch of pm_series_fourier_coef on the same records (the DFT of their
+    residual under the same inner detrend) and pm_series_surrogates by
+    pm_series_surrogates_fourier, which rotates every coefficient's phase and transforms back
+    (surrogates.py); every chunk then goes through the same launches with the same chunking --
+    but that a surrogate of more than 512 records (M >= 2048) counts 16 K nspec n bytes against max_bytes as
+    under "gaussian": the synthesis stores series-contiguously into a second array and transposes
+    (under "gaussian" that array is the residual's).
+    "fourier" together with `until=` is a ValueError: every member would be cut at its own end, so
+    the transform length would be each member's own -- out of scope."""
     from .surrogates import significance  # (surrogates derives from this module)
-    return significance(self, k0, k1, nsur, seed, member0, max_bytes, until)
+    return significance(self, k0, k1, nsur, seed, member0, max_bytes, until, method)
 
