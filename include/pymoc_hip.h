@@ -1410,6 +1410,63 @@ int pm_series_kendall(const struct pm_series_kendall *d, int32_t *conc, int32_t 
                       int32_t *tie, int32_t *nfin, pm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * pm_series_dfa -- the detrended-fluctuation-analysis exponent (Livina & Lenton 2007; the third
+ * indicator of Lenton et al. 2012) of every sliding window, on the device: ONE launch.  (no
+ * counterpart: a rolling Python loop over the downloaded series.)  The series, the record window,
+ * W = window, S = step, detrend and stt are pm_series_windows': the same windows, the same rule
+ * (a window is USED iff all W of its values are finite).  Besides them the entry takes nq scales
+ *   s_0 < s_1 < .. < s_{nq-1},   2 <= nq <= PM_DFA_SCALES_MAX = 16,
+ *   PM_DFA_SCALE_MIN = 4 <= s_0,  4 * s_{nq-1} <= W      (at least four boxes per scale: W >= 20)
+ * and two HOST-made tables of nq doubles, suu and weight (below).
+ * For a used window, every product and sum rounded on its own (-ffp-contract=off), every sum
+ * sequential in ascending order from +0.0:
+ *   pass 1   mean and slope exactly as pm_series_windows forms them (the same order: the same bits)
+ *   d_j      = r_j of pm_series_windows under LINEAR and CONSTANT; under NONE d_j = x_j - mean
+ *              (the profile of DFA is that of the mean-removed series by definition)
+ *   per scale s = s_q:
+ *     nb     = W / s boxes (integer division) from the window's start, box b holding the records
+ *              j = b s + i, i < s; the W - nb s trailing records belong to no box
+ *     u_i    = (double)i - 0.5 * (s - 1)                                     (exact)
+ *     suu_q  = sum u_i^2 = s (s^2 - 1) / 12, the table suu[q]; the entry checks it against its own
+ *              evaluation bit for bit, as it does stt
+ *     the profile y runs over the window from +0.0, y <- y + d_j, and f_q over all boxes of the
+ *     scale from +0.0; per box, sy and su from +0.0:
+ *       pass A   over the box's s records:  y <- y + d_j;  sy <- sy + y;  su <- su + u_i * y
+ *                a = sy / (double)s;  c = su / suu_q
+ *       pass B   y restarts from its value at the box's start; over the same records:
+ *                y <- y + d_j;  e = (y - a) - c * u_i;  f_q <- f_q + e * e
+ *     F2_q   = f_q / (double)(nb * s)
+ *   alpha    = sum_q weight[q] * log(F2_q), sequential in q from +0.0, log the natural logarithm;
+ *              weight[q] = 0.5 (L_q - Lbar) / sum_q (L_q - Lbar)^2 with L_q = ln s_q and Lbar their
+ *              mean: the least-squares slope of ln F against ln s.  The entry checks that the
+ *              weights are finite and sum to zero within rounding (|sum| <= 2^-40 sum |w|).
+ *              alpha is NaN unless every F2_q is finite and > 0 (a constant window, an overflow).
+ * F2_q is defined by IEEE operations alone and is reproduced bit for bit; alpha goes through the
+ * device library's log and is stated to a bound (tests/dfa_cases.py).
+ * Results, members contiguous in each:
+ *   alpha[nwin][nspec][n]
+ *   f2[nq][nwin][nspec][n]    stored iff f2 != NULL
+ * an unused window stores NaN in every plane; each plane is a series that pm_series_kendall and
+ * pm_series_group_stats read as it stands.  (The number of used windows is pm_series_windows'.)
+ * A result depends on that member's values alone, as for pm_series_windows.
+ *
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): what pm_series_windows
+ * checks of n, nspec, nrec, [k0, k1), W, S, K >= W, detrend, stt, nwin * nspec, nspec and the
+ * grid; nq and the scales in the ranges above and strictly ascending; both tables; v and alpha
+ * not NULL.                                                                                    */
+#define PM_DFA_SCALES_MAX 16
+#define PM_DFA_SCALE_MIN 4
+struct pm_series_dfa {
+  int32_t n, nspec, nrec, k0, k1, window, step, detrend, nq, reserved;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  double stt;                            /* W (W^2 - 1) / 12                                      */
+  int32_t scale[PM_DFA_SCALES_MAX];      /* s_q, q < nq (the rest is not read)                    */
+  double suu[PM_DFA_SCALES_MAX];         /* s_q (s_q^2 - 1) / 12                                  */
+  double weight[PM_DFA_SCALES_MAX];      /* of log(F2_q) in alpha                                 */
+};
+int pm_series_dfa(const struct pm_series_dfa *d, double *alpha, double *f2, pm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Surrogate significance of the trends above (pymoc_amd.SeriesSurrogates,
  * SeriesWindows.significance), on the device: ONE launch per entry and chunk of surrogates.  (no
  * counterpart: what a user does with a random generator and a loop over the downloaded series.)

@@ -265,10 +265,12 @@ class TrendSignificance(object):
 
 class Significance(object):
   """What `SeriesWindows.significance` returns: `.var` and `.ac`, a `TrendSignificance` each, and
-  `nsur`."""
+  `nsur`; with the windows' `dfa`, also `.dfa`."""
 
-  def __init__(self, var, ac, nsur):
+  def __init__(self, var, ac, nsur, dfa=None):
     self.var, self.ac, self.nsur = var, ac, nsur
+    if dfa is not None:
+      self.dfa = dfa
 
 
 def chunk_size(nsur, max_bytes, K, nspec, n, per=8):
@@ -304,9 +306,13 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None, method=
   two = method == "fourier" and fourier.wants_scratch(K)
   nbmax = chunk_size(nsur, max_bytes, K, nspec, n, per=16 if gauss or two else 8)
   # 1. the observed trends: `indicators` of the record window (censored into a copy)
-  (out, _), on = sw._indicators(k0, k1, cens=cens)
+  got = sw._indicators(k0, k1, cens=cens)
+  (out, _), on = got[:2]
   shape = (nwin, nspec, n)
-  obs = [launch_kendall(_Plane(out, i, shape), shape, 0, nwin, stream, timer) for i in (2, 3)]
+  series = [_Plane(out, i, shape) for i in (2, 3)]
+  if sw._dfa:  # the observed alpha series, after the two others
+    series.append(_Plane(got[2][0], 0, shape))
+  obs = [launch_kendall(view, shape, 0, nwin, stream, timer) for view in series]
   # 2. the fit of what the windows were cut from (`on`), and the zeroed accumulators
   inner = "constant" if gauss else sw.detrend  # (under "gaussian" `on` is the residual)
   if method == "fourier":  # in place of the fit: the coefficients of the same records
@@ -317,12 +323,13 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None, method=
   else:  # per member, over its records before its end
     fit = launch_fit_ranged(on[0], on[0].shape, on[1], on[2], inner, until.end, stream, timer)
   acc = [[DeviceArray.zeros((nspec, n), np.int32, stream=stream) for _ in range(3)]
-         for _ in range(2)]
+         for _ in obs]
   # 3. chunk by chunk on arrays allocated once for the largest: `indicators` of the surrogates
   y =DeviceArray((K, nbmax * nspec, n), np.float64)
   yres = DeviceArray((K, nbmax * nspec, n), np.float64) if gauss or two else None
   nbad = DeviceArray((nbmax * nspec, n), np.int32) if gauss else None
   wout = alloc_windows(nwin, nbmax * nspec, n)
+  walpha = DeviceArray((nwin, nbmax * nspec, n), np.float64) if sw._dfa else None
   cnt = [DeviceArray((nbmax * nspec, n), np.int32) for _ in range(4)]
   for b0 in range(0, nsur, nbmax):
     nb = min(nbmax, nsur - b0)
@@ -334,15 +341,19 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None, method=
       launch_surrogates(ych, fit, b0, seed, member0, ctx)
     # (cut where the record is, in place; the same smoother the record went through)
     indicators(ych, 0, K, sw._par, ctx, cens=cens, into=ych, weights=gauss,
-               resid=_Plane(yres, 0, ych.shape) if gauss else None, nbad=nbad, out=wout)
+               resid=_Plane(yres, 0, ych.shape) if gauss else None, nbad=nbad, out=wout,
+               dfa=sw._dfa, alpha=walpha)
     wshape = (nwin, planes, n)
-    for i, which in enumerate((2, 3)):
-      launch_kendall(_Plane(wout[0], which, wshape), wshape, 0, nwin, stream, timer, out=cnt)
+    series = [_Plane(wout[0], which, wshape) for which in (2, 3)]
+    if sw._dfa:
+      series.append(_Plane(walpha, 0, wshape))
+    for i, view in enumerate(series):
+      launch_kendall(view, wshape, 0, nwin, stream, timer, out=cnt)
       launch_exceed(obs[i], cnt, (nb, nspec, n), acc[i], stream, timer)
   # 4. the counts, and nothing else
   res = []
-  for i in range(2):
+  for i in range(len(obs)):
     o = [a.download(stream=stream) for a in obs[i][:3]]
     ge, le, nvalid = (a.download(stream=stream) for a in acc[i])
     res.append(TrendSignificance(sw.names, o, ge, le, nvalid))
-  return Significance(res[0], res[1], nsur)
+  return Significance(res[0], res[1], nsur, *res[2:])

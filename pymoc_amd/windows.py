@@ -39,13 +39,24 @@ records allocated per call), and the windows are cut from the residual with only
 removed.  A record that is not finite has a NaN residual, so the windows that hold it are excluded
 as before.
 
+`dfa=True` (or a sequence of scales) adds the third indicator of Lenton et al. 2012, the exponent
+alpha of detrended fluctuation analysis (Livina & Lenton 2007) of every window: one more launch
+(pm_series_dfa, csrc/dfa.hip; dfa.py states what it is) on the same windows of the same series.
+`compute` then also returns `dfa` [name] -> [n, nwin], `dfa_f2` [name] -> [n, nwin, nq] (the mean
+squared fluctuation F2 at every scale) and `dfa_scales`; across_members("dfa") works as for the
+four others; `trend()` and `significance()` gain `.dfa`.  Every F2 equals the restatement
+(tests/dfa_cases.py) bit for bit; alpha goes through the device library's log and is held to a
+bound.  Without `dfa` every method issues the launches it issued before.
+
 Every method goes through `indicators`, the one path from a device series to its indicator planes
-(censor, smooth, the window launch), and `significance` sends the record and every chunk of
-surrogates through it; `launch_windows` and `launch_kendall` are the launches alone, over any
+(censor, smooth, the window launch, the DFA launch), and `significance` sends the record and every
+chunk of surrogates through it; `launch_windows` and `launch_kendall` are the launches alone, over any
 device view (series.py).
 
 Out of scope:
   * skewness and higher moments;
+  * of DFA: backward boxes, orders above 1, overlapping boxes, rescaling alpha to Lenton's
+    "propagator", DFA of `pos`;
   * of the surrogate test: ARMA orders above 1 (the parametric null model is AR(1)), `until=`
     with Fourier surrogates, amplitude-adjusted (AAFT / IAAFT) surrogates, and surrogates of
     `pos`;
@@ -62,6 +73,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
+from .dfa import dfa_par, launch_dfa
 from .series import Series, _Plane, as_int, by_name, records
 from .smooth import Weights, half_width, launch_smooth
 from .stats import SeriesStats
@@ -157,16 +169,18 @@ def launch_windows(x, k0, k1, par, ctx, out=None):
 
 
 def indicators(x, k0, k1, par, ctx, cens=None, into=None, weights=None, resid=None, nbad=None,
-               out=None):
+               out=None, dfa=None, alpha=None, f2=None):
   """The one path from a device series to its indicator planes, for the record and for a chunk of
   surrogates alike: over the records [k0, k1) of the view `x` (K records, any number of planes)
     1. pm_series_censor with the `shifts.Censor` cens, when one is given: into `into` (x itself:
        in place; None: a copy of K records allocated here);
     2. pm_series_smooth with the `smooth.Weights` weights, when they are given: the residual into
        `resid` (None: allocated here), the count into `nbad`;
-    3. pm_series_windows with `par` into `out` (as `launch_windows`).
+    3. pm_series_windows with `par` into `out` (as `launch_windows`);
+    4. pm_series_dfa with `par` and the `dfa.DfaPar` dfa, when one is given, on the view step 3
+       reads: into `alpha` and `f2` (as `dfa.launch_dfa`).
   Returns ((out, nused), (series, r0, r1)): the planes, and the records the windows were cut from,
-  which a null-model fit reads.  Nothing is synchronised."""
+  which a null-model fit reads; with `dfa`, (alpha, f2) as a third.  Nothing is synchronised."""
   K, planes = k1 - k0, tuple(x.shape[1:])
   if cens is not None:
     from .shifts import launch_censor  # (shifts derives from this module)
@@ -177,7 +191,10 @@ def indicators(x, k0, k1, par, ctx, cens=None, into=None, weights=None, resid=No
     resid = DeviceArray((K,) + planes, np.float64) if resid is None else resid
     launch_smooth(x, k0, k1, weights, ctx, resid=resid, nbad=nbad)
     x, k0, k1 = resid, 0, K
-  return launch_windows(x, k0, k1, par, ctx, out=out), (x, k0, k1)
+  res = launch_windows(x, k0, k1, par, ctx, out=out), (x, k0, k1)
+  if dfa is not None:
+    res += (launch_dfa(x, k0, k1, par, dfa, ctx, alpha=alpha, f2=f2),)
+  return res
 
 
 class Trend(object):
@@ -205,26 +222,33 @@ def kendall(source, k0=0, k1=None, stream=None):
 
 class Windows(object):
   """What `compute` returns: mean, slope, var, ac `[name] -> [n, nwin]`, nused `[name] -> [n]` and
-  record_end [nwin]."""
+  record_end [nwin]; with `dfa`, also dfa `[name] -> [n, nwin]`, dfa_f2 `[name] -> [n, nwin, nq]`
+  and dfa_scales."""
 
-  def __init__(self, names, record_end, out, nused):
-    # out [4, nwin, nspec, n]
+  def __init__(self, names, record_end, out, nused, dfa=None):
+    # out [4, nwin, nspec, n]; dfa = (scales, alpha [nwin, nspec, n], f2 [nq, nwin, nspec, n])
     self.names, self.record_end = list(names), record_end
     for i, key in enumerate(INDICATORS):
       setattr(self, key, by_name(self.names, out[i].transpose(1, 2, 0)))
     self.nused = by_name(self.names, nused)
+    if dfa is not None:
+      self.dfa_scales = tuple(dfa[0])
+      self.dfa = by_name(self.names, dfa[1].transpose(1, 2, 0))
+      self.dfa_f2 = by_name(self.names, dfa[2].transpose(2, 3, 1, 0))
 
 
 class WindowTrend(object):
-  """What `trend` returns: `.var` and `.ac`, a `Trend` each."""
+  """What `trend` returns: `.var` and `.ac`, a `Trend` each; with `dfa`, also `.dfa`."""
 
-  def __init__(self, var, ac):
+  def __init__(self, var, ac, dfa=None):
     self.var, self.ac = var, ac
+    if dfa is not None:
+      self.dfa = dfa
 
 
 class SeriesWindows(_Source):
   """`SeriesWindows(source, window, step=1, detrend="linear", lag=1, groups=None, stream=None,
-  sigma=None, truncate=4.0)`.
+  sigma=None, truncate=4.0, dfa=None)`.
 
   source    an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
   window    W, the records of a window, in [4, 4096]; any integer
@@ -236,6 +260,9 @@ class SeriesWindows(_Source):
   truncate  its half-width in sigmas, in [1, 8] (smooth.py); K <= 4096 under "gaussian"
   lag       Lg of the autocorrelation, in [1, W - 2]
   groups    int array [n] of labels, for `across_members` (as SeriesStats)
+  dfa       None, True (the scales `dfa.default_scales(W)`) or a sequence of 2 to 16 strictly
+            ascending integer scales, 4 <= s and 4 s <= W: the DFA exponent of every window as a
+            fifth indicator, "dfa" -- one more launch (pm_series_dfa) per call
 
   Each call of `compute` / `across_members` / `trend` is one launch of pm_series_windows on the
   source's stream (and what follows it on the device), after one of pm_series_smooth under
@@ -243,7 +270,7 @@ class SeriesWindows(_Source):
   of at least W records."""
 
   def __init__(self, source, window, step=1, detrend="linear", lag=1, groups=None, stream=None,
-               sigma=None, truncate=4.0):
+               sigma=None, truncate=4.0, dfa=None):
     _Source.__init__(self, source, stream)
     W, S, Lg = as_int("window", window), as_int("step", step), as_int("lag", lag)
     if not _lib.PM_WIN_MIN <= W <= _lib.PM_WIN_MAX:
@@ -256,6 +283,8 @@ class SeriesWindows(_Source):
     self._smooth = check_detrend(detrend, sigma, truncate)
     self._weights = Weights(self._smooth[0], self._smooth[2]) if self._smooth else None
     self._par = win_par(W, S, Lg, detrend)
+    self._dfa = None if dfa is None else dfa_par(W, dfa)
+    self.dfa_scales = None if dfa is None else self._dfa.scales
     self._fourier_tables = {}  # per K, for significance(method="fourier")
     self.window, self.step, self.lag, self.detrend, self.stt = W, S, Lg, detrend, self._par.stt
     self._set_groups(groups)  # checked now, used by across_members
@@ -298,30 +327,42 @@ class SeriesWindows(_Source):
     return launch_windows(self._series, k0, k1, self._par, self._ctx(), out=out)
 
   def _indicators(self, k0, k1, **kw):
-    """`indicators` of the source series with this object's settings."""
-    return indicators(self._series, k0, k1, self._par, self._ctx(), weights=self._weights, **kw)
+    """`indicators` of the source series with this object's settings (its `dfa` among them: a
+    third result then)."""
+    return indicators(self._series, k0, k1, self._par, self._ctx(), weights=self._weights,
+                      dfa=self._dfa, **kw)
 
   def compute(self, k0=0, k1=None):
     k0, k1, nwin = self._window(k0, k1)
-    (out, nused), _ = self._indicators(k0, k1)
+    res = self._indicators(k0, k1, f2=True if self._dfa else None)
+    out, nused = res[0]
+    dfa = None
+    if self._dfa:
+      dfa = (self._dfa.scales,) + tuple(a.download(stream=self.stream) for a in res[2])
     return Windows(self.names, k0 + np.arange(nwin) * self.step + self.window - 1,
-                   out.download(stream=self.stream), nused.download(stream=self.stream))
+                   out.download(stream=self.stream), nused.download(stream=self.stream), dfa)
 
   def across_members(self, which, k0=0, k1=None, quantiles=()):
     """The statistics, across the members of every group, of the indicator `which` ("mean",
-    "slope", "var" or "ac") as a series with the window for its record: a `stats.GroupStats` whose
+    "slope", "var", "ac", or with `dfa` "dfa") as a series with the window for its record: a `stats.GroupStats` whose
     arrays are [ngroups, nwin] (quantile: [nq, ngroups, nwin]).  A member's unused window is NaN:
     SeriesStats excludes and counts it."""
-    if which not in INDICATORS:
-      raise ValueError("unknown indicator %r (one of %s)" % (which, ", ".join(INDICATORS)))
+    known = INDICATORS + (("dfa",) if self._dfa else ())
+    if which not in known:
+      raise ValueError("unknown indicator %r (one of %s)" % (which, ", ".join(known)))
     k0, k1, nwin = self._window(k0, k1)
     out = self._alloc(nwin)
     # (its argument checks come before the launch)
-    view = _Plane(out[0], INDICATORS.index(which), (nwin, self.nspec, self.n))
+    kw, shape = dict(out=out), (nwin, self.nspec, self.n)
+    if which == "dfa":
+      kw["alpha"] = DeviceArray(shape, np.float64)
+      view = _Plane(kw["alpha"], 0, shape)
+    else:
+      view = _Plane(out[0], INDICATORS.index(which), shape)
     st = SeriesStats((view, self.names), groups=self.groups, quantiles=quantiles,
                      stream=self.stream)
     self.group_labels = st.group_labels
-    self._indicators(k0, k1, out=out)
+    self._indicators(k0, k1, **kw)
     return st.across_members()
 
   def trend(self, k0=0, k1=None):
@@ -329,11 +370,15 @@ class SeriesWindows(_Source):
     launch, then pm_series_kendall over out[2] and out[3] on the device.  NaN windows (unused, or
     ac of a window without variance) are left out of the pairs and show in nfin."""
     k0, k1, nwin = self._trend_window(k0, k1)
-    (out, _), _ = self._indicators(k0, k1)
+    got = self._indicators(k0, k1)
+    out = got[0][0]
     shape = (nwin, self.nspec, self.n)
+    series = [_Plane(out, i, shape) for i in (2, 3)]
+    if self._dfa:  # the alpha series, after the two others
+      series.append(_Plane(got[2][0], 0, shape))
     res = []
-    for i in (2, 3):
-      cnt = launch_kendall(_Plane(out, i, shape), shape, 0, nwin, self.stream, self._timer())
+    for view in series:
+      cnt = launch_kendall(view, shape, 0, nwin, self.stream, self._timer())
       res.append(Trend(self.names, *(a.download(stream=self.stream) for a in cnt)))
     return WindowTrend(*res)
 
@@ -376,7 +421,17 @@ class SeriesWindows(_Source):
     under "gaussian": the synthesis stores series-contiguously into a second array and transposes
     (under "gaussian" that array is the residual's).
     "fourier" together with `until=` is a ValueError: every member would be cut at its own end, so
-    the transform length would be each member's own -- out of scope."""
+    the transform length would be each member's own -- out of scope.
+
+    With `dfa` the result also has `.dfa`, the same test of the trend of the DFA exponent: the
+    observed alpha series and its Kendall counts next to the two others, and per chunk one more
+    launch each of pm_series_dfa (alpha only: F2 is not stored), pm_series_kendall and
+    pm_series_exceed, into a third triple of accumulators -- under either method, `until=` and
+    "gaussian" alike, because it reads the series the window launch reads.  A surrogate costs what
+    it cost against max_bytes (the chunk's window planes do not count, so neither does its alpha
+    plane, 8 nwin nspec n bytes per surrogate next to their 32 nwin nspec n), and on the device
+    one more pass over its windows: about 2 nq W / S reads of LDS per record, against 3 W / S
+    for the var and ac planes."""
     from .surrogates import significance  # (surrogates derives from this module)
     return significance(self, k0, k1, nsur, seed, member0, max_bytes, until, method)
 
