@@ -1467,6 +1467,81 @@ struct pm_series_dfa {
 int pm_series_dfa(const struct pm_series_dfa *d, double *alpha, double *f2, pm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * pm_series_restoring -- the restoring rate lambda of every sliding window under AR(1)-correlated
+ * regression errors (Boers 2021: the increments of the detrended index regressed on the index,
+ * by iterated generalised least squares), on the device: ONE launch.  (no counterpart: a rolling
+ * statsmodels GLSAR fit over the downloaded series.)  The series, the record window, W = window,
+ * S = step, detrend and stt are pm_series_windows': the same windows, the same rule (a window is
+ * USED iff all W of its values are finite).  Besides them the entry takes iters.
+ *   PM_RESTORE_WIN_MIN = 8 <= W <= PM_WIN_MAX;  1 <= iters <= PM_RESTORE_ITERS_MAX = 64
+ * For a used window, every product, sum and quotient rounded on its own (-ffp-contract=off), every
+ * sum sequential in ascending order from +0.0, every expression evaluated as it is parenthesised
+ * (left to right where it is not):
+ *   pass 1   mean and slope exactly as pm_series_windows forms them (the same order: the same bits)
+ *   d_j      = r_j of pm_series_windows under LINEAR and CONSTANT; under NONE d_j = x_j - mean
+ *              (lambda with an intercept does not depend on an offset, and the offset must not
+ *              cost digits)
+ *   N = W - 1;  x_t = d_t,  y_t = d_{t+1} - d_t  for t < N;  M = N - 1
+ *   pass 2   over t = 1 .. N - 1 ascending, with (xc, yc) = (x_t, y_t), (xp, yp) = (x_{t-1},
+ *            y_{t-1}), the fourteen sums
+ *              Sxc = sum xc     Sxp = sum xp     Syc = sum yc     Syp = sum yp
+ *              Sxcxc = sum xc * xc     Sxcxp = sum xc * xp     Sxpxp = sum xp * xp
+ *              Sxcyc = sum xc * yc     Sxcyp = sum xc * yp     Sxpyc = sum xp * yc
+ *              Sxpyp = sum xp * yp     Sycyc = sum yc * yc     Sycyp = sum yc * yp
+ *              Sypyp = sum yp * yp
+ *            x_0 and y_0 are kept aside.  (No expression below reads Sypyp: the squared residuals
+ *            are summed over the current pairs plus the t = 0 term.  An implementation need not
+ *            form it.)  Then, once:  Sxy2 = Sxcyp + Sxpyc;  Sy2 = Syc + Syp;  Sx2 = Sxc + Sxp
+ *   rho_0 = +0.0.  For i = 0 .. iters - 1, a fixed count with no early exit, with r = rho_i and
+ *   Mf = (double)M:
+ *     r2  = r * r
+ *     SX  = Sxc - r * Sxp                                  the sums over t = 1 .. N - 1 of the
+ *     SY  = Syc - r * Syp                                  whitened X* = x_t - r x_{t-1} and
+ *     SXX = (Sxcxc - (2.0 * r) * Sxcxp) + r2 * Sxpxp       Y* = y_t - r y_{t-1}; the first
+ *     SXY = (Sxcyc - r * Sxy2) + r2 * Sxpyp                observation is dropped, as GLSAR's
+ *     mx  = SX / Mf;  my = SY / Mf                         whitening drops it
+ *     lambda_i = (SXY - SX * my) / (SXX - SX * mx)
+ *   and, for i < iters - 1 only (the last lambda needs no further rho):
+ *     a   = (my - lambda_i * mx) / (1.0 - r)               the intercept of the unwhitened model
+ *     e0  = (y_0 - a) - lambda_i * x_0                     its residual at t = 0
+ *     l2  = lambda_i * lambda_i;  al = a * lambda_i;  a2m = Mf * (a * a)
+ *     q   = (((((Sycyc - (2.0 * a) * Syc) - (2.0 * lambda_i) * Sxcyc) + (2.0 * al) * Sxc)
+ *            + l2 * Sxcxc) + a2m) + e0 * e0                = sum_{t < N} e_t^2
+ *     c   = ((((Sycyp - a * Sy2) - lambda_i * Sxy2) + al * Sx2) + l2 * Sxcxp) + a2m
+ *                                                          = sum_{t = 1}^{N-1} e_t e_{t-1}
+ *     rho_{i+1} = c / q      with e_t = y_t - a - lambda_i x_t: the biased lag-1 estimate, as
+ *                            pm_series_windows' ac, so |rho| <= 1 before rounding (statsmodels'
+ *                            GLSAR demeans the residuals and uses the adjusted Yule-Walker
+ *                            estimate; this is not that)
+ *   lam = lambda_{iters-1};  rho = rho_{iters-1}, the rho the stored lambda was fitted with (+0.0
+ *   for iters = 1: ordinary least squares over t >= 1).  Both are NaN unless both are finite.  A
+ *   constant window, a window the line fits exactly (q = 0) and an overflow follow what IEEE
+ *   gives: there is no special case.
+ * lambda is per record interval: lambda = phi - 1 for an AR(1) state with coefficient phi, -dt /
+ * tau for a relaxation time tau sampled every dt; it rises towards 0 as stability is lost.
+ * Neither sqrt, log nor exp is called: lam and rho are defined by IEEE operations alone and are
+ * reproduced bit for bit (tests/restoring_cases.py).
+ * Results, members contiguous in each:
+ *   lam[nwin][nspec][n]
+ *   rho[nwin][nspec][n]    stored iff rho != NULL
+ * an unused window stores NaN in both; each is a series that pm_series_kendall and
+ * pm_series_group_stats read as it stands.  (The number of used windows is pm_series_windows'.)
+ * A result depends on that member's values alone, as for pm_series_windows.
+ *
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): what pm_series_windows
+ * checks of n, nspec, nrec, [k0, k1), S, K >= W, detrend, stt, nwin * nspec, nspec and the grid;
+ * W and iters in the ranges above; v and lam not NULL.                                          */
+#define PM_RESTORE_WIN_MIN 8
+#define PM_RESTORE_ITERS_MAX 64
+struct pm_series_restoring {
+  int32_t n, nspec, nrec, k0, k1, window, step, detrend, iters, reserved;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  double stt;                            /* W (W^2 - 1) / 12                                      */
+};
+int pm_series_restoring(const struct pm_series_restoring *d, double *lam, double *rho,
+                        pm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Surrogate significance of the trends above (pymoc_amd.SeriesSurrogates,
  * SeriesWindows.significance), on the device: ONE launch per entry and chunk of surrogates.  (no
  * counterpart: what a user does with a random generator and a loop over the downloaded series.)

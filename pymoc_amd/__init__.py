@@ -29,6 +29,7 @@ from .indices import RowIndices, IndexRecorder
 from .stats import SeriesStats
 from .spectra import SeriesSpectra
 from .windows import SeriesWindows
+from .restoring import restoring_par, launch_restoring
 from .surrogates import SeriesSurrogates
 from .smooth import SeriesSmooth
 from .shifts import SeriesShifts

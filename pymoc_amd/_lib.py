@@ -366,6 +366,17 @@ class pm_series_dfa(C.Structure):
               ("suu", C.c_double * PM_DFA_SCALES_MAX), ("weight", C.c_double * PM_DFA_SCALES_MAX)]
 
 
+PM_RESTORE_WIN_MIN, PM_RESTORE_ITERS_MAX = 8, 64
+
+
+class pm_series_restoring(C.Structure):
+  """Mirror of `struct pm_series_restoring` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("window", C.c_int32), ("step", C.c_int32),
+              ("detrend", C.c_int32), ("iters", C.c_int32), ("reserved", C.c_int32), ("v", c_dp),
+              ("stt", C.c_double)]
+
+
 class pm_series_kendall(C.Structure):
   """Mirror of `struct pm_series_kendall` (include/pymoc_hip.h)."""
   _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
@@ -566,6 +577,7 @@ SIGNATURES = {
     "pm_series_kendall": (C.c_int, [C.POINTER(pm_series_kendall), c_dp, c_dp, c_dp, c_dp,
                                     C.c_void_p]),
     "pm_series_dfa": (C.c_int, [C.POINTER(pm_series_dfa), c_dp, c_dp, C.c_void_p]),
+    "pm_series_restoring": (C.c_int, [C.POINTER(pm_series_restoring), c_dp, c_dp, C.c_void_p]),
     "pm_series_surrogates": (C.c_int, [C.POINTER(pm_series_surrogates), c_dp, c_dp, C.c_void_p]),
     "pm_series_exceed": (C.c_int, [C.POINTER(pm_series_exceed), c_dp, c_dp, c_dp, C.c_void_p]),
     "pm_series_smooth": (C.c_int, [C.POINTER(pm_series_smooth), c_dp, c_dp, c_dp, C.c_void_p]),

@@ -1,6 +1,7 @@
-// windows_geom.hip.h -- the tile of the two kernels that stage sliding windows in LDS, K22
-// k_series_windows (windows.hip) and K32 k_series_dfa (dfa.hip): host inline functions, one rule
-// for both units, which pm_series_windows_geometry reports.
+// windows_geom.hip.h -- the tile of the three kernels that stage sliding windows in LDS, K22
+// k_series_windows (windows.hip), K33 k_series_dfa (dfa.hip) and K34 k_series_restoring
+// (restoring.hip): host inline functions, one rule for the units, which
+// pm_series_windows_geometry reports.
 #pragma once
 #include "launch.hip.h"
 

@@ -265,12 +265,14 @@ class TrendSignificance(object):
 
 class Significance(object):
   """What `SeriesWindows.significance` returns: `.var` and `.ac`, a `TrendSignificance` each, and
-  `nsur`; with the windows' `dfa`, also `.dfa`."""
+  `nsur`; with the windows' `dfa`, also `.dfa`; with their `restoring`, also `.lam`."""
 
-  def __init__(self, var, ac, nsur, dfa=None):
+  def __init__(self, var, ac, nsur, dfa=None, lam=None):
     self.var, self.ac, self.nsur = var, ac, nsur
     if dfa is not None:
       self.dfa = dfa
+    if lam is not None:
+      self.lam = lam
 
 
 def chunk_size(nsur, max_bytes, K, nspec, n, per=8):
@@ -312,6 +314,8 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None, method=
   series = [_Plane(out, i, shape) for i in (2, 3)]
   if sw._dfa:  # the observed alpha series, after the two others
     series.append(_Plane(got[2][0], 0, shape))
+  if sw._restoring:  # and the observed lambda series, after them
+    series.append(_Plane(got[-1][0], 0, shape))
   obs = [launch_kendall(view, shape, 0, nwin, stream, timer) for view in series]
   # 2. the fit of what the windows were cut from (`on`), and the zeroed accumulators
   inner = "constant" if gauss else sw.detrend  # (under "gaussian" `on` is the residual)
@@ -330,6 +334,7 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None, method=
   nbad = DeviceArray((nbmax * nspec, n), np.int32) if gauss else None
   wout = alloc_windows(nwin, nbmax * nspec, n)
   walpha = DeviceArray((nwin, nbmax * nspec, n), np.float64) if sw._dfa else None
+  wlam = DeviceArray((nwin, nbmax * nspec, n), np.float64) if sw._restoring else None
   cnt = [DeviceArray((nbmax * nspec, n), np.int32) for _ in range(4)]
   for b0 in range(0, nsur, nbmax):
     nb = min(nbmax, nsur - b0)
@@ -342,11 +347,13 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None, method=
     # (cut where the record is, in place; the same smoother the record went through)
     indicators(ych, 0, K, sw._par, ctx, cens=cens, into=ych, weights=gauss,
                resid=_Plane(yres, 0, ych.shape) if gauss else None, nbad=nbad, out=wout,
-               dfa=sw._dfa, alpha=walpha)
+               dfa=sw._dfa, alpha=walpha, restoring=sw._restoring, lam=wlam)
     wshape = (nwin, planes, n)
     series = [_Plane(wout[0], which, wshape) for which in (2, 3)]
     if sw._dfa:
       series.append(_Plane(walpha, 0, wshape))
+    if sw._restoring:
+      series.append(_Plane(wlam, 0, wshape))
     for i, view in enumerate(series):
       launch_kendall(view, wshape, 0, nwin, stream, timer, out=cnt)
       launch_exceed(obs[i], cnt, (nb, nspec, n), acc[i], stream, timer)
@@ -356,4 +363,5 @@ def significance(sw, k0, k1, nsur, seed, member0, max_bytes, until=None, method=
     o = [a.download(stream=stream) for a in obs[i][:3]]
     ge, le, nvalid = (a.download(stream=stream) for a in acc[i])
     res.append(TrendSignificance(sw.names, o, ge, le, nvalid))
-  return Significance(res[0], res[1], nsur, *res[2:])
+  return Significance(res[0], res[1], nsur, dfa=res[2] if sw._dfa else None,
+                      lam=res[-1] if sw._restoring else None)

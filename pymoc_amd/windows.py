@@ -48,8 +48,20 @@ four others; `trend()` and `significance()` gain `.dfa`.  Every F2 equals the re
 (tests/dfa_cases.py) bit for bit; alpha goes through the device library's log and is held to a
 bound.  Without `dfa` every method issues the launches it issued before.
 
+`restoring=True` (or a number of iterations) adds Boers' own indicator, the restoring rate lambda of
+every window: the increments of the detrended index regressed on the index with AR(1)-correlated
+errors, by iterated generalised least squares -- one more launch (pm_series_restoring,
+csrc/restoring.hip; restoring.py states what it is) on the same windows of the same series, after
+the DFA launch.  lambda is per record interval (phi - 1 of an AR(1) state, -dt / tau of a
+relaxation time tau) and rises towards 0 as stability is lost; unlike `ac` and `var` it does not
+rise when the forcing noise merely gets redder.  `compute` then also returns `lam` and `lam_rho`
+(the errors' lag-1 coefficient the stored lambda was fitted with) [name] -> [n, nwin];
+across_members("lam") works as for the others; `trend()` and `significance()` gain `.lam`, after
+`var`, `ac` and `dfa`.  Both equal the restatement (tests/restoring_cases.py) bit for bit.  Without
+`restoring` every method issues the launches it issued before.
+
 Every method goes through `indicators`, the one path from a device series to its indicator planes
-(censor, smooth, the window launch, the DFA launch), and `significance` sends the record and every
+(censor, smooth, the window launch, the DFA launch, the restoring launch), and `significance` sends the record and every
 chunk of surrogates through it; `launch_windows` and `launch_kendall` are the launches alone, over any
 device view (series.py).
 
@@ -57,6 +69,8 @@ Out of scope:
   * skewness and higher moments;
   * of DFA: backward boxes, orders above 1, overlapping boxes, rescaling alpha to Lenton's
     "propagator", DFA of `pos`;
+  * of the restoring rate: AR orders of the errors above 1, online updating, the rate of `pos`,
+    and identifiability where the noise is more persistent than the state (restoring.py);
   * of the surrogate test: ARMA orders above 1 (the parametric null model is AR(1)), `until=`
     with Fourier surrogates, amplitude-adjusted (AAFT / IAAFT) surrogates, and surrogates of
     `pos`;
@@ -74,6 +88,7 @@ from . import _lib
 from ._lib import check, lib
 from .device import DeviceArray, _sh, launch_span
 from .dfa import dfa_par, launch_dfa
+from .restoring import launch_restoring, restoring_par
 from .series import Series, _Plane, as_int, by_name, records
 from .smooth import Weights, half_width, launch_smooth
 from .stats import SeriesStats
@@ -169,7 +184,7 @@ def launch_windows(x, k0, k1, par, ctx, out=None):
 
 
 def indicators(x, k0, k1, par, ctx, cens=None, into=None, weights=None, resid=None, nbad=None,
-               out=None, dfa=None, alpha=None, f2=None):
+               out=None, dfa=None, alpha=None, f2=None, restoring=None, lam=None, rho=None):
   """The one path from a device series to its indicator planes, for the record and for a chunk of
   surrogates alike: over the records [k0, k1) of the view `x` (K records, any number of planes)
     1. pm_series_censor with the `shifts.Censor` cens, when one is given: into `into` (x itself:
@@ -178,9 +193,12 @@ def indicators(x, k0, k1, par, ctx, cens=None, into=None, weights=None, resid=No
        `resid` (None: allocated here), the count into `nbad`;
     3. pm_series_windows with `par` into `out` (as `launch_windows`);
     4. pm_series_dfa with `par` and the `dfa.DfaPar` dfa, when one is given, on the view step 3
-       reads: into `alpha` and `f2` (as `dfa.launch_dfa`).
+       reads: into `alpha` and `f2` (as `dfa.launch_dfa`);
+    5. pm_series_restoring with `par` and the `restoring.RestoringPar` restoring, when one is
+       given, on the same view: into `lam` and `rho` (as `restoring.launch_restoring`).
   Returns ((out, nused), (series, r0, r1)): the planes, and the records the windows were cut from,
-  which a null-model fit reads; with `dfa`, (alpha, f2) as a third.  Nothing is synchronised."""
+  which a null-model fit reads; with `dfa`, (alpha, f2) as a third; with `restoring`, (lam, rho)
+  as the last.  Nothing is synchronised."""
   K, planes = k1 - k0, tuple(x.shape[1:])
   if cens is not None:
     from .shifts import launch_censor  # (shifts derives from this module)
@@ -194,6 +212,8 @@ def indicators(x, k0, k1, par, ctx, cens=None, into=None, weights=None, resid=No
   res = launch_windows(x, k0, k1, par, ctx, out=out), (x, k0, k1)
   if dfa is not None:
     res += (launch_dfa(x, k0, k1, par, dfa, ctx, alpha=alpha, f2=f2),)
+  if restoring is not None:
+    res += (launch_restoring(x, k0, k1, par, restoring, ctx, lam=lam, rho=rho),)
   return res
 
 
@@ -223,10 +243,11 @@ def kendall(source, k0=0, k1=None, stream=None):
 class Windows(object):
   """What `compute` returns: mean, slope, var, ac `[name] -> [n, nwin]`, nused `[name] -> [n]` and
   record_end [nwin]; with `dfa`, also dfa `[name] -> [n, nwin]`, dfa_f2 `[name] -> [n, nwin, nq]`
-  and dfa_scales."""
+  and dfa_scales; with `restoring`, also lam and lam_rho `[name] -> [n, nwin]`."""
 
-  def __init__(self, names, record_end, out, nused, dfa=None):
-    # out [4, nwin, nspec, n]; dfa = (scales, alpha [nwin, nspec, n], f2 [nq, nwin, nspec, n])
+  def __init__(self, names, record_end, out, nused, dfa=None, restoring=None):
+    # out [4, nwin, nspec, n]; dfa = (scales, alpha [nwin, nspec, n], f2 [nq, nwin, nspec, n]);
+    # restoring = (lam, rho), each [nwin, nspec, n]
     self.names, self.record_end = list(names), record_end
     for i, key in enumerate(INDICATORS):
       setattr(self, key, by_name(self.names, out[i].transpose(1, 2, 0)))
@@ -235,20 +256,26 @@ class Windows(object):
       self.dfa_scales = tuple(dfa[0])
       self.dfa = by_name(self.names, dfa[1].transpose(1, 2, 0))
       self.dfa_f2 = by_name(self.names, dfa[2].transpose(2, 3, 1, 0))
+    if restoring is not None:
+      self.lam = by_name(self.names, restoring[0].transpose(1, 2, 0))
+      self.lam_rho = by_name(self.names, restoring[1].transpose(1, 2, 0))
 
 
 class WindowTrend(object):
-  """What `trend` returns: `.var` and `.ac`, a `Trend` each; with `dfa`, also `.dfa`."""
+  """What `trend` returns: `.var` and `.ac`, a `Trend` each; with `dfa`, also `.dfa`; with
+  `restoring`, also `.lam`."""
 
-  def __init__(self, var, ac, dfa=None):
+  def __init__(self, var, ac, dfa=None, lam=None):
     self.var, self.ac = var, ac
     if dfa is not None:
       self.dfa = dfa
+    if lam is not None:
+      self.lam = lam
 
 
 class SeriesWindows(_Source):
   """`SeriesWindows(source, window, step=1, detrend="linear", lag=1, groups=None, stream=None,
-  sigma=None, truncate=4.0, dfa=None)`.
+  sigma=None, truncate=4.0, dfa=None, restoring=None)`.
 
   source    an `IndexRecorder` or `(DeviceArray [nrec, nspec, n], names)` (series.py)
   window    W, the records of a window, in [4, 4096]; any integer
@@ -263,6 +290,10 @@ class SeriesWindows(_Source):
   dfa       None, True (the scales `dfa.default_scales(W)`) or a sequence of 2 to 16 strictly
             ascending integer scales, 4 <= s and 4 s <= W: the DFA exponent of every window as a
             fifth indicator, "dfa" -- one more launch (pm_series_dfa) per call
+  restoring None, True (10 iterations, the published setting) or the number of iterations, 1 to
+            64; W >= 8: the restoring rate lambda of every window under AR(1)-correlated errors
+            (restoring.py), per record interval, as a further indicator, "lam" -- one more launch
+            (pm_series_restoring) per call
 
   Each call of `compute` / `across_members` / `trend` is one launch of pm_series_windows on the
   source's stream (and what follows it on the device), after one of pm_series_smooth under
@@ -270,7 +301,7 @@ class SeriesWindows(_Source):
   of at least W records."""
 
   def __init__(self, source, window, step=1, detrend="linear", lag=1, groups=None, stream=None,
-               sigma=None, truncate=4.0, dfa=None):
+               sigma=None, truncate=4.0, dfa=None, restoring=None):
     _Source.__init__(self, source, stream)
     W, S, Lg = as_int("window", window), as_int("step", step), as_int("lag", lag)
     if not _lib.PM_WIN_MIN <= W <= _lib.PM_WIN_MAX:
@@ -285,6 +316,7 @@ class SeriesWindows(_Source):
     self._par = win_par(W, S, Lg, detrend)
     self._dfa = None if dfa is None else dfa_par(W, dfa)
     self.dfa_scales = None if dfa is None else self._dfa.scales
+    self._restoring = None if restoring is None else restoring_par(W, restoring)
     self._fourier_tables = {}  # per K, for significance(method="fourier")
     self.window, self.step, self.lag, self.detrend, self.stt = W, S, Lg, detrend, self._par.stt
     self._set_groups(groups)  # checked now, used by across_members
@@ -328,26 +360,31 @@ class SeriesWindows(_Source):
 
   def _indicators(self, k0, k1, **kw):
     """`indicators` of the source series with this object's settings (its `dfa` among them: a
-    third result then)."""
+    third result then; and its `restoring`: a last one)."""
     return indicators(self._series, k0, k1, self._par, self._ctx(), weights=self._weights,
-                      dfa=self._dfa, **kw)
+                      dfa=self._dfa, restoring=self._restoring, **kw)
 
   def compute(self, k0=0, k1=None):
     k0, k1, nwin = self._window(k0, k1)
-    res = self._indicators(k0, k1, f2=True if self._dfa else None)
+    res = self._indicators(k0, k1, f2=True if self._dfa else None,
+                           rho=True if self._restoring else None)
     out, nused = res[0]
-    dfa = None
+    dfa = restoring = None
     if self._dfa:
       dfa = (self._dfa.scales,) + tuple(a.download(stream=self.stream) for a in res[2])
+    if self._restoring:
+      restoring = tuple(a.download(stream=self.stream) for a in res[-1])
     return Windows(self.names, k0 + np.arange(nwin) * self.step + self.window - 1,
-                   out.download(stream=self.stream), nused.download(stream=self.stream), dfa)
+                   out.download(stream=self.stream), nused.download(stream=self.stream), dfa,
+                   restoring)
 
   def across_members(self, which, k0=0, k1=None, quantiles=()):
     """The statistics, across the members of every group, of the indicator `which` ("mean",
-    "slope", "var", "ac", or with `dfa` "dfa") as a series with the window for its record: a `stats.GroupStats` whose
+    "slope", "var", "ac", with `dfa` "dfa", with `restoring` "lam") as a series with the window for its record: a `stats.GroupStats` whose
     arrays are [ngroups, nwin] (quantile: [nq, ngroups, nwin]).  A member's unused window is NaN:
     SeriesStats excludes and counts it."""
-    known = INDICATORS + (("dfa",) if self._dfa else ())
+    known = (INDICATORS + (("dfa",) if self._dfa else ())
+             + (("lam",) if self._restoring else ()))
     if which not in known:
       raise ValueError("unknown indicator %r (one of %s)" % (which, ", ".join(known)))
     k0, k1, nwin = self._window(k0, k1)
@@ -357,6 +394,9 @@ class SeriesWindows(_Source):
     if which == "dfa":
       kw["alpha"] = DeviceArray(shape, np.float64)
       view = _Plane(kw["alpha"], 0, shape)
+    elif which == "lam":
+      kw["lam"] = DeviceArray(shape, np.float64)
+      view = _Plane(kw["lam"], 0, shape)
     else:
       view = _Plane(out[0], INDICATORS.index(which), shape)
     st = SeriesStats((view, self.names), groups=self.groups, quantiles=quantiles,
@@ -376,11 +416,14 @@ class SeriesWindows(_Source):
     series = [_Plane(out, i, shape) for i in (2, 3)]
     if self._dfa:  # the alpha series, after the two others
       series.append(_Plane(got[2][0], 0, shape))
+    if self._restoring:  # and the lambda series, after them
+      series.append(_Plane(got[-1][0], 0, shape))
     res = []
     for view in series:
       cnt = launch_kendall(view, shape, 0, nwin, self.stream, self._timer())
       res.append(Trend(self.names, *(a.download(stream=self.stream) for a in cnt)))
-    return WindowTrend(*res)
+    return WindowTrend(res[0], res[1], dfa=res[2] if self._dfa else None,
+                       lam=res[-1] if self._restoring else None)
 
   def significance(self, k0=0, k1=None, nsur=1000, seed=0, member0=None, max_bytes=2 << 30,
                    until=None, method="ar1"):
@@ -431,7 +474,14 @@ class SeriesWindows(_Source):
     it cost against max_bytes (the chunk's window planes do not count, so neither does its alpha
     plane, 8 nwin nspec n bytes per surrogate next to their 32 nwin nspec n), and on the device
     one more pass over its windows: about 2 nq W / S reads of LDS per record, against 3 W / S
-    for the var and ac planes."""
+    for the var and ac planes.
+
+    With `restoring` the result also has `.lam`, the same test of the trend of the restoring rate
+    (per record interval), after the others: the observed lambda series and its Kendall counts,
+    and per chunk one more launch each of pm_series_restoring (lam only: rho is not stored),
+    pm_series_kendall and pm_series_exceed -- under either method, `until=` and "gaussian" alike,
+    for the same reason.  Its plane, 8 nwin nspec n bytes per surrogate, does not count against
+    max_bytes either; on the device it costs one more pass of 2 W / S reads of LDS per record."""
     from .surrogates import significance  # (surrogates derives from this module)
     return significance(self, k0, k1, nsur, seed, member0, max_bytes, until, method)
 
