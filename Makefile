@@ -7,7 +7,7 @@ HIPHDR = $(wildcard $(CSRC)/*.h) include/pymoc_hip.h
 all: lib oracle
 
 HIPCFLAGS = --offload-arch=$(ARCH) -O3 -ffp-contract=off -fPIC -std=c++17 -Wno-unused-value $(EXTRA)
-HIPOBJ = $(CSRC)/build/pymoc_hip.o $(CSRC)/build/exact_div.o $(CSRC)/build/column_g16.o $(CSRC)/build/column_g32.o $(CSRC)/build/column_g64.o $(CSRC)/build/column_implicit.o $(CSRC)/build/equi.o $(CSRC)/build/equi_column.o $(CSRC)/build/jn2018_fast.o $(CSRC)/build/jn2018_implicit.o $(CSRC)/build/sections.o $(CSRC)/build/steady.o $(CSRC)/build/forcing.o $(CSRC)/build/noise.o $(CSRC)/build/indices.o $(CSRC)/build/overturning.o $(CSRC)/build/twobasin_overturning.o $(CSRC)/build/stats.o $(CSRC)/build/spectra.o $(CSRC)/build/windows.o $(CSRC)/build/dfa.o $(CSRC)/build/restoring.o $(CSRC)/build/surrogates.o $(CSRC)/build/fourier.o $(CSRC)/build/smooth.o $(CSRC)/build/shifts.o
+HIPOBJ = $(CSRC)/build/pymoc_hip.o $(CSRC)/build/exact_div.o $(CSRC)/build/column_g16.o $(CSRC)/build/column_g32.o $(CSRC)/build/column_g64.o $(CSRC)/build/column_implicit.o $(CSRC)/build/equi.o $(CSRC)/build/equi_column.o $(CSRC)/build/jn2018_fast.o $(CSRC)/build/jn2018_implicit.o $(CSRC)/build/sections.o $(CSRC)/build/steady.o $(CSRC)/build/forcing.o $(CSRC)/build/noise.o $(CSRC)/build/indices.o $(CSRC)/build/overturning.o $(CSRC)/build/twobasin_overturning.o $(CSRC)/build/stats.o $(CSRC)/build/spectra.o $(CSRC)/build/windows.o $(CSRC)/build/dfa.o $(CSRC)/build/restoring.o $(CSRC)/build/eof.o $(CSRC)/build/surrogates.o $(CSRC)/build/fourier.o $(CSRC)/build/smooth.o $(CSRC)/build/shifts.o
 
 lib: pymoc_amd/libpymoc_hip.so
 $(CSRC)/build/%.o: $(CSRC)/%.hip $(HIPHDR)

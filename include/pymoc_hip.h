@@ -1843,6 +1843,107 @@ struct pm_series_surrogates_fourier {
 int pm_series_surrogates_fourier(const struct pm_series_surrogates_fourier *d, double *y,
                                  pm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The leading EOF of several indices of a recorded series and its principal component
+ * (pymoc_amd.SeriesEOF; Held & Kleinen 2004, "degenerate fingerprinting"), on the device: THREE
+ * entries, one launch each.  (no counterpart: the download of the series and one
+ * np.linalg.eigh per member.)  The series is v[k][s][m] as above, the record window [k0, k1),
+ * K = k1 - k0 >= 2.  sel[q] holds q DISTINCT indices in [0, nspec), in any order,
+ * 1 <= q <= PM_EOF_Q_MAX = 32; x_kj = v[k0 + k][sel[j]][m].  w[q][n] holds per-(index, member)
+ * weights on the device; NULL: every weight is 1.0 (a product with 1.0 is exact: the same bits).
+ * A UNIT is what shares one EOF: every member on its own (order, start and unit NULL, nu = n), or
+ * a group of members, unit u = order[start[u] .. start[u+1] - 1], (order, start) as
+ * pm_series_group_stats takes them, unit[m] the unit of member m.
+ * Throughout: every product, sum and quotient is rounded on its own (-ffp-contract=off); every
+ * sum is sequential in ascending order from +0.0; an argmax or a max is the FIRST on ties:
+ *   first argmax of z_0 .. z_{q-1}:   p = 0; for i = 1 .. q - 1: if z_i > z_p then p = i
+ *   first max of z_0 .. z_{q-1}:      the value z_p of that p
+ * (a NaN never compares greater: a NaN z_0 stays, a later NaN is passed over).
+ * Neither sqrt, log nor exp is called: every result is defined by IEEE operations alone and is
+ * reproduced bit for bit by the NumPy restatement (tests/eof_cases.py).
+ *
+ * 1. pm_series_scatter -- per member m:
+ *   record k is USED iff all q values x_kj are finite (isfinite)
+ *   nused[m]   (int32) the number of used records
+ *   mean_j   = (sum over the used k of x_kj) / (double)nused
+ *   a_kj     = (x_kj - mean_j) * w_jm
+ *   S_ij     = sum over the used k of a_ki * a_kj,  0 <= j <= i < q
+ *   stores nused[n], mean[q][n], scat[q (q + 1) / 2][n] with S_ij at entry i (i + 1) / 2 + j;
+ *   with nused < 2 every mean and every scat entry of the member is NaN.
+ *
+ * 2. pm_series_eof -- per unit u (q, n, nu, iters; nused and scat as entry 1 stored them):
+ *   the members of u are taken in `order`; those with nused < 2 are skipped
+ *   N        = the sum of their nused (int32), stored as ntot[u]
+ *   P_ij     = the sum of their S_ij
+ *   C_ij     = P_ij / (double)N for j <= i, C_ji = C_ij
+ *   trace    = sum_i C_ii, stored as it is
+ *   if N == 0, or trace is not finite, or trace <= 0: eof, lam, resid and vv are NaN.  Otherwise
+ *   p0       = the first argmax of C_ii;  y_i = C_{i,p0}
+ *   exactly `iters` times, a fixed count with no early exit, 1 <= iters <= PM_EOF_ITERS_MAX = 1024:
+ *     p      = the first argmax of |y_i|
+ *     if y_p is zero or not finite: eof, lam, resid and vv are NaN, and the iteration ends
+ *     v_i    = y_i / y_p            (v_p is exactly 1: the sign is fixed, the largest loading is
+ *                                    positive)
+ *     y_i    = sum_j C_ij * v_j
+ *   then once more p, the same test of y_p, v_i = y_i / y_p and y_i = sum_j C_ij * v_j, and
+ *   vy       = sum_i v_i * y_i;  vv = sum_i v_i * v_i;  lam = vy / vv    (the Rayleigh quotient)
+ *   resid    = (the first max over i of |y_i - lam * v_i|) / |lam|
+ *   stores eof[q][nu] (= v), lam[nu], trace[nu], resid[nu], vv[nu], ntot[nu] (int32).
+ *   resid is the caller's read-out of convergence: the iteration count is fixed so that a result is
+ *   a pure function of its input, and whether `iters` sufficed shows in resid, not in the count
+ *   (two equal leading eigenvalues give a deterministic result with a large resid).  lam / trace
+ *   is the fraction of variance the mode holds.
+ *
+ * 3. pm_series_project -- per member m, u = unit[m] (m itself with unit NULL), per record k of the
+ * window:
+ *   pc[k][0][m] = sum_j ((x_kj - mean_jm) * w_jm) * eof_j[u]        for a used record
+ *   NaN for an unused record, for nused[m] < 2 and wherever an eof_j[u] is NaN
+ *   pc is a device series [K][1][n] that every pm_series_* entry reads as it stands.
+ *   The EOF is normalised to a largest loading of 1, not to unit length (that would take a sqrt):
+ *   pc is the unit-length component times the constant sqrt(vv).  ac, the DFA exponent, the
+ *   restoring rate and Kendall's tau do not see the scale; var scales by vv, which entry 2 returns.
+ * A result of entries 1 and 3 depends on that member's values (and its unit's EOF) alone: not on
+ * n, the shard or the launch geometry.
+ *
+ * Checked before anything is launched (PM_EINVAL, outputs untouched): n, nspec, nrec >= 1 and
+ * 0 <= k0 < k1 <= nrec (entries 1 and 3); K >= 2; q and iters in the ranges above; every sel in
+ * [0, nspec) and no two equal; no NULL pointer but w, and order, start, start_dev and unit, which
+ * are NULL together (entry 2: then nu = n; entry 3: unit NULL needs nu = n); 1 <= nu <= n; start[0]
+ * = 0, start monotone, start[nu] = n, no unit larger than PM_STATS_GROUP_MAX; K < 2^30 and the
+ * grids below 2^31 blocks.  The checks read the HOST mirror start; the kernel reads start_dev.
+ * That order is a permutation and that unit agrees with it are the caller's to ensure.          */
+#define PM_EOF_Q_MAX 32
+#define PM_EOF_ITERS_MAX 1024
+struct pm_series_scatter {
+  int32_t n, nspec, nrec, k0, k1, q, reserved1, reserved2;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  const double *w;                       /* device [q][n], or NULL: 1.0                           */
+  int32_t sel[PM_EOF_Q_MAX];             /* sel[j], j < q (the rest is not read)                  */
+};
+int pm_series_scatter(const struct pm_series_scatter *d, int32_t *nused, double *mean,
+                      double *scat, pm_stream_t stream);
+struct pm_series_eof {
+  int32_t n, q, nu, iters;
+  const int32_t *nused;                  /* device [n]                                            */
+  const double *scat;                    /* device [q (q + 1) / 2][n]                             */
+  const int32_t *order;                  /* device [n], or NULL: every member a unit              */
+  const int32_t *start;                  /* HOST [nu + 1], or NULL                                */
+  const int32_t *start_dev;              /* DEVICE, the same values, or NULL                      */
+};
+int pm_series_eof(const struct pm_series_eof *d, double *eof, double *lam, double *trace,
+                  double *resid, double *vv, int32_t *ntot, pm_stream_t stream);
+struct pm_series_project {
+  int32_t n, nspec, nrec, k0, k1, q, nu, reserved;
+  const double *v;                       /* device [nrec][nspec][n]                               */
+  const double *w;                       /* device [q][n], or NULL: 1.0                           */
+  const int32_t *nused;                  /* device [n]                                            */
+  const double *mean;                    /* device [q][n]                                         */
+  const double *eof;                     /* device [q][nu]                                        */
+  const int32_t *unit;                   /* device [n], or NULL: unit[m] = m                      */
+  int32_t sel[PM_EOF_Q_MAX];
+};
+int pm_series_project(const struct pm_series_project *d, double *pc, pm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

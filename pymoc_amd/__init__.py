@@ -30,6 +30,7 @@ from .stats import SeriesStats
 from .spectra import SeriesSpectra
 from .windows import SeriesWindows
 from .restoring import restoring_par, launch_restoring
+from .eof import SeriesEOF
 from .surrogates import SeriesSurrogates
 from .smooth import SeriesSmooth
 from .shifts import SeriesShifts

@@ -377,6 +377,32 @@ class pm_series_restoring(C.Structure):
               ("stt", C.c_double)]
 
 
+PM_EOF_Q_MAX, PM_EOF_ITERS_MAX = 32, 1024
+
+
+class pm_series_scatter(C.Structure):
+  """Mirror of `struct pm_series_scatter` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("q", C.c_int32), ("reserved1", C.c_int32),
+              ("reserved2", C.c_int32), ("v", c_dp), ("w", c_dp),
+              ("sel", C.c_int32 * PM_EOF_Q_MAX)]
+
+
+class pm_series_eof(C.Structure):
+  """Mirror of `struct pm_series_eof` (include/pymoc_hip.h); `start` is a HOST address."""
+  _fields_ = [("n", C.c_int32), ("q", C.c_int32), ("nu", C.c_int32), ("iters", C.c_int32),
+              ("nused", c_dp), ("scat", c_dp), ("order", c_dp), ("start", C.c_void_p),
+              ("start_dev", c_dp)]
+
+
+class pm_series_project(C.Structure):
+  """Mirror of `struct pm_series_project` (include/pymoc_hip.h)."""
+  _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
+              ("k1", C.c_int32), ("q", C.c_int32), ("nu", C.c_int32), ("reserved", C.c_int32),
+              ("v", c_dp), ("w", c_dp), ("nused", c_dp), ("mean", c_dp), ("eof", c_dp),
+              ("unit", c_dp), ("sel", C.c_int32 * PM_EOF_Q_MAX)]
+
+
 class pm_series_kendall(C.Structure):
   """Mirror of `struct pm_series_kendall` (include/pymoc_hip.h)."""
   _fields_ = [("n", C.c_int32), ("nspec", C.c_int32), ("nrec", C.c_int32), ("k0", C.c_int32),
@@ -578,6 +604,9 @@ SIGNATURES = {
                                     C.c_void_p]),
     "pm_series_dfa": (C.c_int, [C.POINTER(pm_series_dfa), c_dp, c_dp, C.c_void_p]),
     "pm_series_restoring": (C.c_int, [C.POINTER(pm_series_restoring), c_dp, c_dp, C.c_void_p]),
+    "pm_series_scatter": (C.c_int, [C.POINTER(pm_series_scatter), c_dp, c_dp, c_dp, C.c_void_p]),
+    "pm_series_eof": (C.c_int, [C.POINTER(pm_series_eof)] + [c_dp] * 6 + [C.c_void_p]),
+    "pm_series_project": (C.c_int, [C.POINTER(pm_series_project), c_dp, C.c_void_p]),
     "pm_series_surrogates": (C.c_int, [C.POINTER(pm_series_surrogates), c_dp, c_dp, C.c_void_p]),
     "pm_series_exceed": (C.c_int, [C.POINTER(pm_series_exceed), c_dp, c_dp, c_dp, C.c_void_p]),
     "pm_series_smooth": (C.c_int, [C.POINTER(pm_series_smooth), c_dp, c_dp, c_dp, C.c_void_p]),
